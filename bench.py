@@ -1,7 +1,18 @@
 """SMEM-seeding benchmark (BASELINE.json metric) on 1..N MI355X.
 
     python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--genome-profile uniform|human]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run does what the headline needs and no more: it builds or loads the
+index, puts the reads in HBM, warms up, times K steps, writes the last step's
+outputs when --dump-outputs names a directory (dump_outputs below), and prints
+one JSON line: metric, value, unit, ms_per_step (wall milliseconds per timed
+step), the workload and the kernel's own times.  Everything else described
+here -- `streaming`, `roofline`, `cpu_baseline`, `parity_sample`, the sa /
+chain / alignment / sw stages, `e2e` and the other genome profile -- runs only
+with --full, after the headline and never inside its timed region, and is
+added to the same line.
 
 Workload (BASELINE.json configs[1], the default --config c2): an FM index
 resident in HBM and 1M x 150 bp single-end reads per GPU (2% substitutions,
@@ -92,8 +103,11 @@ CONFIGS = {
 }
 
 
+T_START = time.time()
+
+
 def log(*a):
-    print("[bench]", *a, file=sys.stderr, flush=True)
+    print(f"[bench {time.time() - T_START:6.1f}s]", *a, file=sys.stderr, flush=True)
 
 
 def parse(argv=None):
@@ -101,6 +115,14 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run and report everything else: roofline and parity sample (CPU "
+                        "oracle), CPU baselines, streaming, the sa / chain / alignment / sw stages, bwa mem end to end "
+                        "against the reference, the other genome profile")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (the arrays Batch.fetch() returns: interval lists "
+                        "and smem_next2 call counts) as DIR/<name>.npy in float64 / float32, at most 64 MB: per-read "
+                        "counts of every read and the full lists of a fixed seeded sample of reads")
     p.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     p.add_argument("--reads", type=int, default=1_000_000, help="resident reads per GPU (the metric's batch)")
     p.add_argument("--read-len", type=int, default=None)
@@ -148,6 +170,8 @@ def parse(argv=None):
                         "profiles/traffic.json, or profiles/traffic_human.json for the human-like profile)")
     p.add_argument("--ceiling-json", default=os.path.join(ROOT, "profiles", "gather_ceiling.json"))
     a = p.parse_args(argv)
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     cfg = CONFIGS[a.config]
     a.read_len = a.read_len or cfg["read_len"]
     a.sub = cfg["sub"] if a.sub is None else a.sub
@@ -186,29 +210,37 @@ def make_genome(args):
     return synth.make_genome(n_bp, seed=args.seed, n_chrom=24)
 
 
-def get_index(args, rank, barrier, device=0):
+def get_index(args, rank, barrier, device=0, need_sa=True):
     """Index (+ .sa) and the genome codes, built once per host by rank 0 and
     cached; every rank then reads them (the genome through a memory map, so
-    no rank regenerates it)."""
+    no rank regenerates it).  need_sa=False: the .sa is neither required in
+    the cache nor read (None is returned in its place)."""
     import smemgpu
     os.makedirs(args.cache, exist_ok=True)
     base = genome_key(args)
     key, skey, gkey = base + ".bwt", base + ".sa", base + ".codes"
-    if rank == 0 and not all(os.path.exists(k) for k in (key, skey, gkey)):
+    built = None
+    if rank == 0 and not all(os.path.exists(k) for k in ((key, skey, gkey) if need_sa else (key, gkey))):
         t = time.time()
         g = make_genome(args)
+        t_g = time.time()
         idx, sa = smemgpu.Index.build_sa(g.codes, sa_intv=32, gpu=args.builder == "gpu", device=device)
+        t_b = time.time()
         idx.write(key + ".tmp")
         sa.write(skey + ".tmp")
         g.codes.tofile(gkey + ".tmp")
         for k in (key, skey, gkey):
             os.replace(k + ".tmp", k)
         del g
+        built = (idx, sa)
         log(f"index built ({args.builder}, {args.genome_profile}): {idx.words.nbytes / 1e6:.1f} MB .bwt + "
-            f"{sa.samples.nbytes / 1e6:.1f} MB .sa in {time.time() - t:.1f} s")
+            f"{sa.samples.nbytes / 1e6:.1f} MB .sa in {time.time() - t:.1f} s (genome {t_g - t:.1f}, build "
+            f"{t_b - t_g:.1f}, cache files {time.time() - t_b:.1f})")
     barrier()
     codes = np.memmap(gkey, dtype=np.uint8, mode="r")
-    return smemgpu.Index.read(key), key, smemgpu.SA.read(skey), codes
+    if built:   # the same bytes as the files just written
+        return built[0], key, built[1] if need_sa else None, codes
+    return smemgpu.Index.read(key), key, smemgpu.SA.read(skey) if need_sa else None, codes
 
 
 def shard_blocks(n_reads: int, rank: int, world: int, block: int = BLOCK) -> list:
@@ -230,7 +262,9 @@ def make_reads(args, rank, genome_codes, world: int = 1, n_reads: int | None = N
     kw = dict(sub_rate=args.sub, n_rate=0.001)
     r = synth.make_read_blocks(np.asarray(genome_codes), blocks, block, args.read_len,
                                seed=1000 + args.seed * 7919 + salt, pairs=bool(getattr(args, "pairs", False)), **kw)
-    return r.subset(np.arange(n)) if r.n > n else r
+    if r.n > n:   # the first n reads (what r.subset(np.arange(n)) holds, without its pass over every read)
+        r = synth.Reads(r.lens[:n].copy(), r.codes[:int(r.offs[n])].copy(), r.offs[:n + 1].astype(np.int64))
+    return r
 
 
 def cpu_leg(args, gpu, opt, idx, idx_path, reads, cores, sw_tasks=None):
@@ -934,6 +968,57 @@ def roofline(args, bpr, bpr64, ostats, n_counted, reads_n, k_ms, a_ms, build_id,
     return out
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: all files together stay under this
+DUMP_READS = 32768        # reads whose lists are written in full (fewer when they would not fit)
+
+
+def _gather(off: np.ndarray, pick: np.ndarray) -> tuple:
+    """(indices of the entries of the picked reads' lists in read order, their
+    offsets rebased to 0) for lists laid out by off[n + 1]."""
+    a = off[pick]
+    ln = off[pick + 1] - a
+    new_off = np.concatenate([[0], np.cumsum(ln)])
+    return np.repeat(a - new_off[:-1], ln) + np.arange(int(new_off[-1])), new_off
+
+
+def dump_outputs(path: str, batch, seed: int, rank: int = 0) -> None:
+    """--dump-outputs: what the batch's last run left in HBM, as a caller gets
+    it from Batch.fetch() (smem_batch_fetch + smem_batch_results), in float
+    arrays (every value is an integer below 2^53, float64 holds it exactly):
+      intv_per_read, calls_per_read   float32 [n_reads]: list lengths of every read
+      sample_reads                    float64 [m]: a fixed seeded sample of read numbers, ascending
+      intv, intv_off                  float64 [k, 4], [m + 1]: the sample's bwtintv_t (x0, x1, x2, info)
+      call_n, call_off                float64 [c], [m + 1]: entries per smem_next2 call of the sample's reads
+    Ranks past 0 write <name>_rank<r>.npy."""
+    from smemgpu.lib import FETCH_INTV
+    res = batch.fetch(mask=FETCH_INTV)
+    intv_off, call_off = res.intv_off.astype(np.int64), res.call_off.astype(np.int64)
+    n = intv_off.size - 1
+    per_read, calls = np.diff(intv_off), np.diff(call_off)
+    out = {}
+    budget = DUMP_BYTES - 7 * 256   # .npy headers
+    if 8 * n <= budget // 4:
+        out["intv_per_read"] = per_read.astype(np.float32)
+        out["calls_per_read"] = calls.astype(np.float32)
+        budget -= 8 * n
+    # the sample: the longest prefix of a seeded order of the reads whose lists fit
+    order = np.random.default_rng([seed, 0x44554d50]).permutation(n)[:DUMP_READS]
+    cost = np.cumsum(24 + 32 * per_read[order] + 8 * calls[order])
+    pick = np.sort(order[:int(np.searchsorted(cost, budget - 16, side="right"))])
+    ii, ioff = _gather(intv_off, pick)
+    ci, coff = _gather(call_off, pick)
+    out["sample_reads"] = pick.astype(np.float64)
+    out["intv"] = res.intv[ii].astype(np.float64)
+    out["intv_off"] = ioff.astype(np.float64)
+    out["call_n"] = res.call_n[ci].astype(np.float64)
+    out["call_off"] = coff.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), arr)
+    log(f"outputs of the last step written to {path}: {len(pick)} of {n} reads in full, "
+        f"{sum(a.nbytes for a in out.values()) / 1e6:.1f} MB")
+
+
 def time_seeding(args, d, gpu, reads, opt) -> dict:
     """The timed region of a seeding step (see the module docstring): W warmup
     steps (the alone launches give kernel_ms_alone), then K steps between
@@ -1004,6 +1089,9 @@ def time_seeding(args, d, gpu, reads, opt) -> dict:
     elapsed = time.perf_counter() - t0
     st = batch.stats()
     value, elapsed_max = aggregate(d, elapsed, reads.n, args.steps)
+    if getattr(args, "dump_outputs", None):
+        # steps are dealt round-robin: the last one ran on this worker's batch
+        dump_outputs(args.dump_outputs, batches[(args.steps - 1) % len(batches)], args.seed, d.rank)
     for b in batches[1:]:
         b.close()
     a_ms = float(np.mean(alone_ms))
@@ -1027,6 +1115,7 @@ def profile_report(args, d, cores, profile: str) -> dict:
     h = copy.copy(args)
     h.genome_profile = profile
     h.traffic_json = traffic_path(profile)
+    h.dump_outputs = None   # the dump is the headline's
     t = time.time()
     idx, idx_path, sa, genome_codes = get_index(h, d.rank, d.barrier, d.gpu)
     t_index = time.time() - t
@@ -1071,10 +1160,86 @@ def main():
     if world > 1:  # the CPU baseline is an N=1 record (rank 0); N>1 lines carry null
         args.cpu_seconds = 0.0
 
-    idx, idx_path, sa, genome_codes = get_index(args, rank, barrier, d.gpu)
+    # the headline: set up, warm up, time the steps (and write their outputs);
+    # everything after it that is not the line's own bookkeeping needs --full
+    idx, idx_path, sa, genome_codes = get_index(args, rank, barrier, d.gpu, need_sa=args.full)
     reads = make_reads(args, rank, genome_codes, world)
     gpu = smemgpu.Gpu(idx, device=d.gpu, lanes_per_cu=args.lanes_per_cu, variant=args.variant, kmer_k=args.kmer_k)
     gpu_variant = gpu.variant
+    opt = smemgpu.Options(min_seed_len=args.min_seed_len)
+    log(f"index in HBM, {reads.n} reads made")
+    T = time_seeding(args, d, gpu, reads, opt)
+    batch, st, value, elapsed_max = T["batch"], T["st"], T["value"], T["elapsed_max"]
+    log(f"{args.steps} steps timed: {elapsed_max / args.steps * 1e3:.3f} ms per step")
+
+    out = None
+    if rank == 0:
+        cfg = CONFIGS[args.config]
+        out = {
+            "metric": METRIC,
+            "value": round(value, 1),
+            "unit": "reads/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u64",
+            "data": "synthetic",
+            "full": bool(args.full),
+            "config": {
+                "workload": f"{args.config}: synthetic {args.genome_mbp:g} Mbp genome index in HBM "
+                            f"({args.genome_profile} repeat profile; stand-in for human_g1k_v37), "
+                            f"{reads.n} x {args.read_len} bp {'PE (interleaved mates)' if args.pairs else 'SE'} reads "
+                            f"resident per GPU, {args.sub:.0%} subs, 0.1% N, k={args.min_seed_len} r=1.5 s=10",
+                "config": args.config,
+                "config_what": cfg["what"],
+                "genome_profile": args.genome_profile,
+                "reads_per_gpu": reads.n,
+                "read_len": args.read_len,
+                "genome_bp": int(args.genome_mbp * 1e6),
+                "index_bytes": int(idx.words.nbytes),
+                "seed": args.seed,
+                "parallelism": f"reads sharded over {world} GPU(s) in blocks of {BLOCK} dealt round-robin, index "
+                               f"replicated, no collectives; {args.streams} host workers per GPU, each running whole "
+                               f"steps on its own stream",
+                "grid": st["grid"], "block": st["block"],
+                "kernel_variant": gpu_variant, "kernel": kernel_name(gpu_variant), "kmer_k": args.kmer_k,
+            },
+            "kernel_ms": round(T["k_ms"], 3),
+            "kernel_busy_ms": round(T["busy_ms"], 3),
+            "kernel_ms_alone": round(T["a_ms"], 3),
+            "compact_ms": round(T["compact_alone"], 3),
+            "overflow_reads": st["n_overflow"],
+            "build_id": smemgpu.build_id(),
+            "kernel_id": smemgpu.kernel_id(),
+            "build_id_matches_sources": smemgpu.build_id() == smemgpu.source_hash(),
+        }
+    if args.full:
+        held = {"idx": idx, "sa": sa}
+        del idx, sa
+        full_report(args, d, out, held, idx_path, genome_codes, reads, gpu, gpu_variant, opt, T)
+    else:
+        batch.close()
+        gpu.close()
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    d.close()
+    log("done")
+
+
+def full_report(args, d, out, held, idx_path, genome_codes, reads, gpu, gpu_variant, opt, T) -> None:
+    """--full: everything the benchmark measures and checks beside the
+    headline, added to the line `out` (rank 0's; None on the other ranks).
+    `held` holds the only references to the host index and .sa ("idx", "sa"),
+    dropped before the other profile loads its own.  Closes the headline's
+    batch and device handle on the way."""
+    import smemgpu
+    idx, sa = held["idx"], held["sa"]
+    rank, world, barrier = d.rank, d.world, d.barrier
+    batch, st, value = T["batch"], T["st"], T["value"]
     # the .sa upload + device densification, timed synchronously here (the
     # binding runs it in the background beside bwa's index load)
     os.environ["SMEM_GPU_SYNC_INIT"] = "1"
@@ -1082,9 +1247,6 @@ def main():
     gpu.load_sa(sa)
     t_sa = time.perf_counter() - t_sa
     del os.environ["SMEM_GPU_SYNC_INIT"]
-    opt = smemgpu.Options(min_seed_len=args.min_seed_len)
-    T = time_seeding(args, d, gpu, reads, opt)
-    batch, st, value, elapsed_max = T["batch"], T["st"], T["value"], T["elapsed_max"]
 
     # streaming (PCIe-inclusive) on every rank, then its aggregate; the
     # config's target read count, or the resident reads (c2)
@@ -1109,7 +1271,7 @@ def main():
         del pac
         sw_rep, sw_tasks = sw_report(gpu, np.asarray(genome_codes))
 
-    out = None
+    cores = None
     if rank == 0:
         inv = cpu_inventory()
         cores = inv["use"]
@@ -1119,58 +1281,21 @@ def main():
             sw_rep["cpu_baseline"] = sw_cpu_rep
         if aln_rep is not None and args.cpu_seconds > 0:
             aln_rep["cpu_baseline"] = aln_cpu(args, idx_path, reads, genome_codes, opt)
-        cfg = CONFIGS[args.config]
-        out = {
-            "metric": METRIC,
-            "value": round(value, 1),
-            "unit": "reads/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"{args.config}: synthetic {args.genome_mbp:g} Mbp genome index in HBM "
-                            f"({args.genome_profile} repeat profile; stand-in for human_g1k_v37), "
-                            f"{reads.n} x {args.read_len} bp {'PE (interleaved mates)' if args.pairs else 'SE'} reads "
-                            f"resident per GPU, {args.sub:.0%} subs, 0.1% N, k={args.min_seed_len} r=1.5 s=10",
-                "config": args.config,
-                "config_what": cfg["what"],
-                "genome_profile": args.genome_profile,
-                "reads_per_gpu": reads.n,
-                "read_len": args.read_len,
-                "genome_bp": int(args.genome_mbp * 1e6),
-                "index_bytes": int(idx.words.nbytes),
-                "seed": args.seed,
-                "parallelism": f"reads sharded over {world} GPU(s) in blocks of {BLOCK} dealt round-robin, index "
-                               f"replicated, no collectives; {args.streams} host workers per GPU, each running whole "
-                               f"steps on its own stream",
-                "grid": st["grid"], "block": st["block"],
-                "kernel_variant": gpu_variant, "kernel": kernel_name(gpu_variant), "kmer_k": args.kmer_k,
-            },
+        out.update({
             "roofline": roofline(args, bpr, bpr64, ostats, n_counted, reads.n, T["k_ms"], T["a_ms"], smemgpu.build_id(),
                                  T["busy_ms"], T["clock_check"], {"grid": st["grid"], "block": st["block"],
                                                                   "variant": gpu_variant}),
             "cpu_baseline": cpu,
             "parity_sample": parity,
-            "compact_ms": round(T["compact_alone"], 3),
             "streaming": srep,
             "sa_lookup": sa_rep,
             "chaining": chain_rep,
             "alignment": aln_rep,
             "sw_extension": sw_rep,
-            "overflow_reads": st["n_overflow"],
             "sa_load": {"s": round(t_sa, 3), "densify": os.environ.get("SMEM_GPU_DENSIFY", "hop"),
                         "what": ".sa upload (every 32nd row) + densification to every 4th row on the device, "
                                 "synchronous"},
-            "build_id": smemgpu.build_id(),
-            "kernel_id": smemgpu.kernel_id(),
-            "build_id_matches_sources": smemgpu.build_id() == smemgpu.source_hash(),
-        }
+        })
     batch.close()
     gpu.close()
     # the product path end to end and the other genome profile: one GPU (the
@@ -1184,11 +1309,9 @@ def main():
                 del creads
         if args.other_profile:
             del idx, sa
+            held.clear()
             other = "uniform" if args.genome_profile == "human" else "human"
             out["uniform" if other == "uniform" else "human_like"] = profile_report(args, d, cores, other)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    d.close()
 
 
 if __name__ == "__main__":

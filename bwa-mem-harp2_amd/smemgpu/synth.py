@@ -110,11 +110,86 @@ HUMAN_REPEATS = (
 )
 
 
+WORKERS = 16   # threads of make_genome_human_like's bulk steps (numpy releases the GIL in them)
+
+
+def _worker_rng(state: dict, steps: int) -> np.random.Generator:
+    """A generator `steps` 64-bit draws ahead of the PCG64 state `state`."""
+    w = np.random.PCG64()
+    w.state = state
+    w.advance(steps)
+    return np.random.Generator(w)
+
+
+def _skip(rng: np.random.Generator, state: dict, steps: int) -> None:
+    """Leave rng where `steps` 64-bit draws by random() after `state` leave it:
+    advance() drops the half draw that 32-bit draws keep for their next call,
+    random() does not."""
+    bg = rng.bit_generator
+    bg.advance(steps)
+    bg.state = dict(bg.state, has_uint32=state["has_uint32"], uinteger=state["uinteger"])
+
+
+def _run(pool, fn, cuts, *more) -> list:
+    return [f.result() for f in [pool.submit(fn, a, b, *m) for a, b, *m in zip(cuts[:-1], cuts[1:], *more)]]
+
+
+def _random_codes(rng: np.random.Generator, n: int, pool=None) -> np.ndarray:
+    """rng.integers(0, 4, size=n, dtype=np.uint8), the same bytes: a code takes
+    8 bits of a 32-bit draw and two 32-bit draws one 64-bit step, so with a
+    pool the array is cut at multiples of 8 codes, each slice drawn from a copy
+    of rng's PCG64 advanced to its first step, and rng itself draws the tail."""
+    st = rng.bit_generator.state
+    if pool is None or n < (1 << 24) or not isinstance(rng.bit_generator, np.random.PCG64) or st["has_uint32"]:
+        return rng.integers(0, 4, size=n, dtype=np.uint8)
+    g = np.empty(n, dtype=np.uint8)
+    cuts = (np.linspace(0, n // 8, 4 * WORKERS + 1).astype(np.int64) * 8).tolist()
+
+    def fill(a, b):
+        g[a:b] = _worker_rng(st, a // 8).integers(0, 4, size=b - a, dtype=np.uint8)
+
+    _run(pool, fill, cuts)
+    _skip(rng, st, cuts[-1] // 8)
+    g[cuts[-1]:] = rng.integers(0, 4, size=n - cuts[-1], dtype=np.uint8)
+    return g
+
+
+def _diverge(copies: np.ndarray, div: np.ndarray, rng: np.random.Generator, pool=None) -> None:
+    """hit = rng.random(copies.shape) < div[:, None]; copies[hit] = (copies[hit] +
+    rng.integers(1, 4, size=hit.sum(), dtype=np.uint8)) & 3 -- the same draws in
+    the same order.  With a pool the rows are cut into slices, each compared
+    against doubles from a copy of rng's PCG64 advanced to the slice's first
+    draw (a double takes one 64-bit step), so the bytes do not depend on it."""
+    n, F = copies.shape
+    if pool is None or n * F < (1 << 20) or not isinstance(rng.bit_generator, np.random.PCG64):
+        hit = rng.random((n, F)) < div[:, None]
+        copies[hit] = (copies[hit] + rng.integers(1, 4, size=int(hit.sum()), dtype=np.uint8)) & 3
+        return
+    st = rng.bit_generator.state
+    hit = np.empty((n, F), dtype=bool)
+    cuts = np.linspace(0, n, WORKERS + 1).astype(np.int64).tolist()
+
+    def fill(a, b):
+        np.less(_worker_rng(st, a * F).random((b - a, F)), div[a:b, None], out=hit[a:b])
+        return int(np.count_nonzero(hit[a:b]))
+
+    counts = _run(pool, fill, cuts)
+    _skip(rng, st, n * F)
+    add = rng.integers(1, 4, size=sum(counts), dtype=np.uint8)
+    first = np.concatenate([[0], np.cumsum(counts)]).tolist()
+
+    def apply(a, b, o, k):
+        c, h = copies[a:b], hit[a:b]
+        c[h] = (c[h] + add[o:o + k]) & 3
+
+    _run(pool, apply, cuts, first[:-1], counts)
+
+
 def _scatter_copies(g: np.ndarray, fam: np.ndarray, n_copies: int, div_lo: float, div_hi: float, trunc: float,
-                    rng: np.random.Generator) -> int:
+                    rng: np.random.Generator, pool=None) -> int:
     """Write n_copies diverged (and 5'-truncated) copies of fam at random
-    positions of g, half of them reverse-complemented; vectorised per
-    family.  Returns the bases written."""
+    positions of g, half of them reverse-complemented.  Returns the bases
+    written."""
     F = fam.size
     n = g.size
     if n_copies <= 0 or F >= n:
@@ -122,17 +197,17 @@ def _scatter_copies(g: np.ndarray, fam: np.ndarray, n_copies: int, div_lo: float
     keep = np.maximum((F * (trunc + (1 - trunc) * rng.random(n_copies))).astype(np.int64), 1)
     div = div_lo + (div_hi - div_lo) * rng.random(n_copies)
     copies = np.broadcast_to(fam, (n_copies, F)).copy()
-    hit = rng.random((n_copies, F)) < div[:, None]
-    copies[hit] = (copies[hit] + rng.integers(1, 4, size=int(hit.sum()), dtype=np.uint8)) & 3
+    _diverge(copies, div, rng, pool)
     rc = rng.random(n_copies) < 0.5
-    copies[rc] = (3 - copies[rc])[:, ::-1]
     starts = (rng.random(n_copies) * (n - F)).astype(np.int64)
-    # copy c keeps its last keep[c] bases (columns F-keep .. F-1 before the flip)
-    col = np.arange(F)[None, :]
-    mask = col >= (F - keep)[:, None]
-    mask[rc] = mask[rc][:, ::-1]
-    rows, cols = np.nonzero(mask)
-    g[starts[rows] + cols] = copies[rows, cols]
+    # copy c keeps its last keep[c] bases: they land at starts[c] + F - keep[c], or, reverse-complemented,
+    # at starts[c]; written copy by copy in order, a later copy over an earlier one
+    dst = np.where(rc, starts, starts + F - keep)
+    for c, (s, k, r) in enumerate(zip(dst.tolist(), keep.tolist(), rc.tolist())):
+        if r:
+            np.subtract(3, copies[c, F - k:][::-1], out=g[s:s + k])
+        else:
+            g[s:s + k] = copies[c, F - k:]
     return int(keep.sum())
 
 
@@ -159,7 +234,7 @@ def _satellites(g: np.ndarray, frac: float, rng: np.random.Generator) -> None:
         for per, L in zip(period, ln):
             unit = rng.integers(0, 4, size=int(per), dtype=np.uint8)
             p = int(rng.integers(0, n - int(L)))
-            g[p:p + int(L)] = np.resize(unit, int(L))
+            g[p:p + int(L)] = np.tile(unit, -(-int(L) // int(per)))[:int(L)]
         budget -= int(ln.sum())
 
 
@@ -171,7 +246,9 @@ def make_genome_human_like(n_bp: int, seed: int = 1, n_chrom: int = 24, satellit
     and simple-sequence arrays.  human_g1k_v37 is ~50 % repeats; the default
     make_genome has 2 %."""
     rng = np.random.default_rng([seed, 0x48554d])
-    g = rng.integers(0, 4, size=n_bp, dtype=np.uint8)
+    from concurrent.futures import ThreadPoolExecutor
+    pool = ThreadPoolExecutor(max_workers=WORKERS)
+    g = _random_codes(rng, n_bp, pool)
     for _name, frac, (lo, hi), n_fam, (dlo, dhi), trunc in HUMAN_REPEATS:
         budget = int(n_bp * frac)
         fams = [rng.integers(0, 4, size=int(rng.integers(lo, hi + 1)), dtype=np.uint8) for _ in range(n_fam)]
@@ -184,11 +261,13 @@ def make_genome_human_like(n_bp: int, seed: int = 1, n_chrom: int = 24, satellit
             n_cp = int(budget * share / max(mean_keep, 1))
             while n_cp > 0:   # bounded temporaries: at most ~64 MB of copies at a time
                 step = max(1, min(n_cp, (64 << 20) // f.size))
-                _scatter_copies(g, f, step, dlo, dhi, trunc, rng)
+                _scatter_copies(g, f, step, dlo, dhi, trunc, rng, pool)
                 n_cp -= step
+    pool.shutdown()
     _satellites(g, satellite_frac, rng)
     n_chrom = max(1, min(n_chrom, n_bp // 1000 if n_bp >= 1000 else 1))
-    cuts = np.sort(rng.choice(np.arange(1, n_bp), size=n_chrom - 1, replace=False)) if n_chrom > 1 else np.array([], dtype=np.int64)
+    # 1 + an index into 1 .. n_bp-1: what choice() draws from np.arange(1, n_bp), without the 8 x n_bp bytes
+    cuts = np.sort(1 + rng.choice(n_bp - 1, size=n_chrom - 1, replace=False)) if n_chrom > 1 else np.array([], dtype=np.int64)
     starts = np.concatenate([[0], cuts, [n_bp]]).astype(np.int64)
     return Genome(g, [f"chr{i + 1}" for i in range(n_chrom)], starts)
 

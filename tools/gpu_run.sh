@@ -11,14 +11,14 @@
 #   traffic[:ARGS]    tools/traffic.py for this build (TCC_EA0_RDREQ per launch) -> traffic.json,
 #                     copied to profiles/traffic_human.json (the default human-like workload) or, with
 #                     --genome-profile,uniform, profiles/traffic.json
-#   bench[:ARGS]      python bench.py ARGS                           -> bench<k>.json / .err
+#   bench[:ARGS]      python bench.py --full ARGS (the whole record)  -> bench<k>.json / .err
 #   rocprof[:ARGS]    rocprofv3 --kernel-trace --stats over bench.py's timed seeding steps -> prof<k>/
 #   pmc:PASSES[:ARGS] tools/pmc_passes.sh, passes "1,2" of its list, ARGS for tools/prof_run.py (bench workload
 #                     args, --variant, --launches) -> pmc<k>/
 #   stamps[:ARGS]     tools/stamps.py (variant-9 cycle split)        -> stamps<k>.log
 #   aln[:ARGS] / chain[:ARGS]   tools/aln_prof.py / tools/chain_prof.py under rocprofv3 --kernel-trace --stats
 #   py:SCRIPT[:ARGS]  python SCRIPT ARGS                              -> py<k>.log
-#   dist2[:ARGS]      bench.py --gpus 2 ARGS under torch.distributed.run, two ranks (on a one-GPU box both
+#   dist2[:ARGS]      bench.py --gpus 2 --full ARGS under torch.distributed.run, two ranks (on a one-GPU box both
 #                     share cuda:0 over gloo: the driver's N>1 launch line rehearsed) -> dist2_<k>.json / .err
 #   env:VAR=v[,VAR=v] exported for the steps after it (e.g. env:PMC_PROG=tools/aln_prof.py,PMC_KERNEL=aln_kernel)
 # Replaces round 2's one-off tools/gpu_r02*.sh scripts (their outputs are under profiles/r02/).
@@ -51,7 +51,7 @@ for step in "$@"; do
       if [ "$prof" = human ]; then cp "$OUT/traffic$k.json" profiles/traffic_human.json
       else cp "$OUT/traffic$k.json" profiles/traffic.json; fi ;;
     bench)
-      timeout -k 10 1000 python -u bench.py $args > "$OUT/bench$k.json" 2> "$OUT/bench$k.err" \
+      timeout -k 10 1000 python -u bench.py --full $args > "$OUT/bench$k.json" 2> "$OUT/bench$k.err" \
         || { echo "bench failed"; tail -5 "$OUT/bench$k.err"; exit $k; } ;;
     rocprof)
       timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof$k" -o run -- \
@@ -70,7 +70,7 @@ for step in "$@"; do
         python3 -u tools/${name}_prof.py $args > "$OUT/$name$k.log" 2>&1 || { echo "$name failed"; exit $k; } ;;
     dist2)
       timeout -k 10 900 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29533 bench.py --gpus 2 $args > "$OUT/dist2_$k.json" 2> "$OUT/dist2_$k.err" \
+        --master-port 29533 bench.py --gpus 2 --full $args > "$OUT/dist2_$k.json" 2> "$OUT/dist2_$k.err" \
         || { echo "dist2 failed"; tail -5 "$OUT/dist2_$k.err"; exit $k; } ;;
     env)
       export $args ;;
