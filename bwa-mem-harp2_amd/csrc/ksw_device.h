@@ -406,6 +406,15 @@ struct SwOut {
 // inside the block.  The row maximum of H1 (padding included) feeds the
 // suboptimal list b (kept one entry per lane, slot = index / 64) and the
 // best row; qe is the smallest column holding the best row's maximum.
+//
+// o_ins = 0 is the exception: the lazy-F loop's exit test, F - e_ins <=
+// max(H, F) - oe_ins in every lane, then holds at its first step, so the
+// reference raises only the first column of each block, by the F its
+// left neighbour's pass 1 ended with.  That is the in-block maximum of the
+// block before; the keyed prefix maximum up to q - 1 holds the block of
+// column q - 1, which is the own block inside a block and the one before at
+// its first column, so one expression (fk) gives both; the choice between it
+// and the full prefix maximum is the same for the whole wave.
 template <class QF, class TF>
 __device__ __forceinline__ SwOut sw_pass_wave(int p, int qlen, QF qsym, int tlen, TF tsym, const int8_t* mat,
                                               int o_del, int e_del, int o_ins, int e_ins, int minsc, int endsc,
@@ -414,6 +423,7 @@ __device__ __forceinline__ SwOut sw_pass_wave(int p, int qlen, QF qsym, int tlen
     const bool u8 = p == 16;
     const int slen = (qlen + p - 1) / p, qp = slen * p;
     const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
+    const bool zi = o_ins == 0;
     uint32_t sc[4];
     int sc4[4], hp[4], ee[4], hm[4], sg[4], tv[4];
 #pragma unroll
@@ -463,8 +473,9 @@ __device__ __forceinline__ SwOut sw_pass_wave(int p, int qlen, QF qsym, int tlen
             const int xa = imax(wave_shr1(ia, NEG), carry_a);
             carry_b = imax(carry_b, rl(ib, 63));
             carry_a = imax(carry_a, rl(ia, 63));
-            const int fb = (xb >> 20) == sg[c] ? imax(0, (xb & 0xfffff) - oe_ins - (q - 1) * e_ins) : 0;
-            const int fa = imax(0, xa - oe_ins - (q - 1) * e_ins);
+            const int fk = imax(0, (xb & 0xfffff) - oe_ins - (q - 1) * e_ins);  // (0 at q = 0: NEG's low bits are 0)
+            const int fb = (xb >> 20) == sg[c] ? fk : 0;
+            const int fa = zi ? fk : imax(0, xa - oe_ins - (q - 1) * e_ins);
             const int h1 = imax(d, fb);
             if (valid) {
                 rmax = imax(rmax, h1);
@@ -548,7 +559,8 @@ __device__ __forceinline__ SwAlign sw_align_wave(int qlen, QF qsym, int tlen, TF
                                                  int e_del, int o_ins, int e_ins, int xtra, int shift, int top) {
     const int p = (xtra & SW_XBYTE) ? 16 : 8;
     const int minsc = (xtra & SW_XSUBO) ? xtra & 0xffff : 0x10000;
-    const SwOut r = sw_pass_wave(p, qlen, qsym, tlen, tsym, mat, o_del, e_del, o_ins, e_ins, minsc, 0x10000, shift, top);
+    const int endsc = (xtra & SW_XSTOP) ? xtra & 0xffff : 0x10000;
+    const SwOut r = sw_pass_wave(p, qlen, qsym, tlen, tsym, mat, o_del, e_del, o_ins, e_ins, minsc, endsc, shift, top);
     SwAlign a{r.score, r.te, r.qe, r.score2, r.te2, -1, -1};
     if ((xtra & SW_XSTART) == 0 || ((xtra & SW_XSUBO) && r.score < (xtra & 0xffff)) || r.qe < 0) return a;
     const int qe = r.qe, te = r.te;

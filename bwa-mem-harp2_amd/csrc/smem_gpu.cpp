@@ -1883,9 +1883,8 @@ int smem_ksw_align2(smem_gpu_t* g, int n, const smem_ksw_atask_t* tasks, const u
         if (k.qlen < 1 || k.qlen > 256 || k.tlen < 0 || k.tlen > 256 || k.q_off + (uint64_t)k.qlen > q_bytes ||
             k.t_off + (uint64_t)k.tlen > t_bytes)
             return fail(SMEM_E_ARG, "smem_ksw_align2: task outside 1 <= qlen <= 256, tlen <= 256 or its pools");
-        // a byte-scored problem must not overflow 255 from below the bias (ksw_align2's callers size
-        // XBYTE for that; a saturated u8 score is returned as 255, as ksw_u8 does)
     }
+    // (a byte score that reaches the ceiling is returned as 255 with qe = -1, as ksw_u8 does: tests' kswa_sat sets)
     for (uint64_t k = 0; k < q_bytes; ++k)
         if (q[k] > 4) return fail(SMEM_E_ARG, "smem_ksw_align2: query code > 4");
     if (kernel_ms) *kernel_ms = 0.0;

@@ -54,11 +54,14 @@ void orc_sw_shift_top(const int8_t *mat, int *shift, int *top)
 	*shift = (uint8_t)(256 - sh);
 }
 
-/* one ksw_u8 (p = 16) or ksw_i16 (p = 8) run; xtra as there */
+/* one ksw_u8 (p = 16) or ksw_i16 (p = 8) run; xtra as there.  full_f (tests
+ * only) takes the early exit out of the lazy-F loop, so F crosses every block
+ * boundary to the end of the row: what the reference would compute if its exit
+ * test never held early, which differs from it only at o_ins = 0 */
 extern __thread uint64_t orc_cells_ext, orc_cells_sw;  /* ksw_oracle.c */
 
 static swr_t sw_pass(int p, int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat,
-		int o_del, int e_del, int o_ins, int e_ins, int xtra)
+		int o_del, int e_del, int o_ins, int e_ins, int xtra, int full_f)
 {
 	const int slen = (qlen + p - 1) / p, qp = slen * p, oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
 	const int minsc = (xtra & XSUBO) ? xtra & 0xffff : 0x10000;
@@ -112,7 +115,7 @@ static swr_t sw_pass(int p, int qlen, const uint8_t *query, int tlen, const uint
 					f[l] = subs(f[l], e_ins);
 					if (f[l] > subs(h, oe_ins)) done = 0;
 				}
-				if (done) goto end_lazy;
+				if (done && !full_f) goto end_lazy;
 			}
 		}
 end_lazy:
@@ -154,25 +157,41 @@ end_lazy:
 }
 
 /* ksw_align2 (software/ksw.c:342-364) */
-static swr_t sw_align(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const orc_aln_opt_t *o, int xtra);
+static swr_t sw_align(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const orc_aln_opt_t *o, int xtra,
+		int full_f);
 
 /* ksw_align2 of one problem, for the tests: out = kswr_t {score, te, qe, score2, te2, tb, qb} */
-void orc_ksw_align2(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
-		int e_del, int o_ins, int e_ins, int xtra, int32_t out[7])
+static void ksw_align2_one(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat,
+		int o_del, int e_del, int o_ins, int e_ins, int xtra, int full_f, int32_t out[7])
 {
 	orc_aln_opt_t o;
 	swr_t r;
 	memset(&o, 0, sizeof(o));
 	memcpy(o.mat, mat, 25);
 	o.o_del = o_del, o.e_del = e_del, o.o_ins = o_ins, o.e_ins = e_ins;
-	r = sw_align(qlen, query, tlen, target, &o, xtra);
+	r = sw_align(qlen, query, tlen, target, &o, xtra, full_f);
 	out[0] = r.score, out[1] = r.te, out[2] = r.qe, out[3] = r.score2, out[4] = r.te2, out[5] = r.tb, out[6] = r.qb;
 }
 
-static swr_t sw_align(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const orc_aln_opt_t *o, int xtra)
+void orc_ksw_align2(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
+		int e_del, int o_ins, int e_ins, int xtra, int32_t out[7])
+{
+	ksw_align2_one(qlen, query, tlen, target, mat, o_del, e_del, o_ins, e_ins, xtra, 0, out);
+}
+
+/* the same with F carried across every block (sw_pass's full_f): not the reference's
+ * answer at o_ins = 0; the tests use it to count the problems where the two differ */
+void orc_ksw_align2_fullf(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const int8_t *mat, int o_del,
+		int e_del, int o_ins, int e_ins, int xtra, int32_t out[7])
+{
+	ksw_align2_one(qlen, query, tlen, target, mat, o_del, e_del, o_ins, e_ins, xtra, 1, out);
+}
+
+static swr_t sw_align(int qlen, const uint8_t *query, int tlen, const uint8_t *target, const orc_aln_opt_t *o, int xtra,
+		int full_f)
 {
 	const int p = (xtra & XBYTE) ? 16 : 8;
-	swr_t r = sw_pass(p, qlen, query, tlen, target, o->mat, o->o_del, o->e_del, o->o_ins, o->e_ins, xtra), rr;
+	swr_t r = sw_pass(p, qlen, query, tlen, target, o->mat, o->o_del, o->e_del, o->o_ins, o->e_ins, xtra, full_f), rr;
 	uint8_t *rq, *rt;
 	int i;
 	if ((xtra & XSTART) == 0 || ((xtra & XSUBO) && r.score < (xtra & 0xffff)) || r.qe < 0) return r;
@@ -180,7 +199,7 @@ static swr_t sw_align(int qlen, const uint8_t *query, int tlen, const uint8_t *t
 	rt = malloc(tlen > 0 ? tlen : 1);
 	for (i = 0; i <= r.qe; ++i) rq[i] = query[r.qe - i];
 	for (i = 0; i < tlen; ++i) rt[i] = i <= r.te ? target[r.te - i] : target[i];
-	rr = sw_pass(p, r.qe + 1, rq, tlen, rt, o->mat, o->o_del, o->e_del, o->o_ins, o->e_ins, XSTOP | r.score);
+	rr = sw_pass(p, r.qe + 1, rq, tlen, rt, o->mat, o->o_del, o->e_del, o->o_ins, o->e_ins, XSTOP | r.score, full_f);
 	free(rq); free(rt);
 	if (r.score == rr.score) r.tb = r.te - rr.te, r.qb = r.qe - rr.qe;
 	return r;
@@ -261,7 +280,7 @@ static int chain2aln_short(const orc_aln_opt_t *o, int64_t l_pac, const uint8_t 
 	if (qe - qb >= SHORT_LEN || re - rb >= SHORT_LEN) return 1;
 	rseq = get_seq(l_pac, pac, rb, re, &rlen);
 	xtra = XSUBO | XSTART | ((qe - qb) * o->a < 250 ? XBYTE : 0) | (o->min_seed_len * o->a);
-	x = sw_align(qe - qb, query + qb, (int)(re - rb), rseq, o, xtra);
+	x = sw_align(qe - qb, query + qb, (int)(re - rb), rseq, o, xtra, 0);
 	free(rseq);
 	if (x.tb < SHORT_EXT >> 1 || x.te > re - rb - (SHORT_EXT >> 1)) return 1;
 	a = reg_push(av);

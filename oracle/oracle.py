@@ -111,6 +111,8 @@ def load() -> C.CDLL:
         lib.orc_ksw_align2.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.POINTER(C.c_int32)]
         lib.orc_ksw_align2.restype = None
+        lib.orc_ksw_align2_fullf.argtypes = lib.orc_ksw_align2.argtypes
+        lib.orc_ksw_align2_fullf.restype = None
         _lib = lib
     return _lib
 
@@ -373,19 +375,22 @@ def ksw(batch) -> np.ndarray:
     return out[:tasks.size]
 
 
-def ksw_align2(batch) -> np.ndarray:
+def ksw_align2(batch, full_f: bool = False) -> np.ndarray:
     """The restatement's ksw_align2 (aln_oracle.c sw_align) of every task of a
-    synth.KswBatch of KSWA_TASK problems, as synth.KSWA_RESULT."""
+    synth.KswBatch of KSWA_TASK problems, as synth.KSWA_RESULT.  full_f (tests
+    only): the lazy-F loop without its early exit, which is not the reference's
+    answer at o_ins = 0."""
     from smemgpu import synth
     lib = load()
+    fn = lib.orc_ksw_align2_fullf if full_f else lib.orc_ksw_align2
     mat = np.ascontiguousarray(batch.mat, dtype=np.int8)
     out = np.zeros(batch.tasks.size, dtype=synth.KSWA_RESULT)
     r = (C.c_int32 * 7)()
     for i, t in enumerate(batch.tasks):
         q = np.ascontiguousarray(batch.q[int(t["q_off"]):int(t["q_off"]) + int(t["qlen"])])
         tg = np.ascontiguousarray(batch.t[int(t["t_off"]):int(t["t_off"]) + int(t["tlen"])])
-        lib.orc_ksw_align2(int(t["qlen"]), q.ctypes.data, int(t["tlen"]), tg.ctypes.data if tg.size else None,
-                           mat.ctypes.data, batch.o_del, batch.e_del, batch.o_ins, batch.e_ins, int(t["xtra"]), r)
+        fn(int(t["qlen"]), q.ctypes.data, int(t["tlen"]), tg.ctypes.data if tg.size else None, mat.ctypes.data,
+           batch.o_del, batch.e_del, batch.o_ins, batch.e_ins, int(t["xtra"]), r)
         out[i] = tuple(r)
     return out
 

@@ -24,13 +24,18 @@ reference code itself:
   ksw.smkt.gz         5000 SW extension problems (include/smem_formats.h) shaped like
                       mem_chain2aln's left/right extensions on g1 (software/bwamem.c:1120-1170)
   ksw.smkr.gz         the reference's own ksw_extend2 on each (software/ksw.c:379)
+  ksw_gap0.smk[tr].gz 500 more with both gap opens 0, and the reference's results
 
     python tests/golden/make_golden.py --chains-only   # (re)make only the g1 .smch files
     python tests/golden/make_golden.py --g2-only       # (re)make only the g2 set
     python tests/golden/make_golden.py --ksw-only      # (re)make only the ksw set
+    python tests/golden/make_golden.py --ksw-gap0-only # (re)make only ksw_gap0
     python tests/golden/make_golden.py --kswa-only     # (re)make only the ksw_align2 sets
   kswa_a<1|2>.smat.gz 3000 ksw_align2 problems shaped like mem_chain2aln_short's (a = 1, 2)
   kswa_a<1|2>.smar.gz the reference's own ksw_align2 on each (software/ksw.c:342)
+  kswa_<set>.sma[tr].gz  up to 600 each (KSWA_MORE): o_ins = 0 at a = 1 and 2, asymmetric gaps,
+                      o_del = 0, KSW_XSTOP, 200-256 bp queries, the length edges and the
+                      longest suboptimal list, byte saturation at a = 2 and a = 1
 """
 import gzip
 import hashlib
@@ -270,12 +275,196 @@ def make_ksw():
                 gz_write(os.path.join(HERE, name + ".gz"), fh.read())
     finally:
         shutil.rmtree(tmp)
+    make_ksw_gap0()
+
+
+def make_ksw_gap0():
+    """ksw_gap0.smkt/.smkr: 500 extension problems with both gap opens 0 (e = 1)"""
+    if not oracle.ref_available():
+        oracle.build(ref=True)
+    tmp = tempfile.mkdtemp()
+    try:
+        with gzip.open(os.path.join(HERE, "g1.fa.gz"), "rb") as fh:
+            from tests import golden_data
+            g = golden_data.fasta_codes(fh.read())
+        b = synth.make_ksw_tasks(g, 500, seed=122)
+        b.o_del = b.o_ins = 0
+        p = os.path.join(tmp, "ksw_gap0.smkt")
+        synth.write_smkt(p, b)
+        oracle.ref_ksw(p, os.path.join(tmp, "ksw_gap0.smkr"))
+        for name in ("ksw_gap0.smkt", "ksw_gap0.smkr"):
+            with open(os.path.join(tmp, name), "rb") as fh:
+                gz_write(os.path.join(HERE, name + ".gz"), fh.read())
+    finally:
+        shutil.rmtree(tmp)
 
 
 # ksw_align2 (software/ksw.c:342), the DP of mem_chain2aln_short: mem_opt_init's
 # scoring (a 1, b 4, gaps 6 + 1: byte problems) and -A 2 scaled (a 2, b 8,
 # gaps 12 + 2: queries of 125 bp and more take ksw_i16)
 KSWA_SETS = [("kswa_a1", 1, 4, 6, 1, 151), ("kswa_a2", 2, 8, 12, 2, 152)]
+
+
+X_BYTE, X_STOP, X_SUBO, X_START = synth.KSW_XBYTE, synth.KSW_XSTOP, synth.KSW_XSUBO, synth.KSW_XSTART
+
+
+def _kswa_batch(items, a, b, o_del, e_del, o_ins, e_ins):
+    """KswBatch of (query, target, xtra) items under one scoring"""
+    tasks = np.zeros(len(items), dtype=synth.KSWA_TASK)
+    qo = to = 0
+    for k, (q, t, xtra) in enumerate(items):
+        tasks[k] = (qo, to, q.size, t.size, xtra, 0)
+        qo += q.size
+        to += t.size
+    cat = lambda xs: np.concatenate([np.asarray(x, dtype=np.uint8) for x in xs]) if xs else np.zeros(0, np.uint8)
+    return synth.KswBatch(tasks, cat([i[0] for i in items]), cat([i[1] for i in items]), synth.bwa_scmat(a, b),
+                          o_del, e_del, o_ins, e_ins)
+
+
+def _short_pair(G, rng, qlo, qhi, sub, indel, n_runs=0, fit=False, exact=False):
+    """One mem_chain2aln_short-shaped pair: a read of qlo..qhi bp copied from the
+    genome with substitutions and indels (synth._mutated_copy), n_runs extra
+    runs of 2..6 inserted bases (an insertion that crosses a block of the
+    striped query is what the lazy-F loop carries), against the reference
+    span padded and shifted by up to 50 (fit: never cut short of the read's
+    end while 256 bp hold it; exact: the mutated read is of the drawn length
+    itself); 30 % on the reverse strand"""
+    ql = int(rng.integers(qlo, qhi + 1))
+    pos = int(rng.integers(300, G.size - ql - 300))
+    read = synth._mutated_copy(G[pos:pos + ql + (40 if exact else 0)], rng, sub, indel)
+    if exact:
+        read = read[:ql]
+        assert read.size == ql
+    for _ in range(n_runs):
+        at = int(rng.integers(1, max(2, read.size)))
+        read = np.concatenate([read[:at], rng.integers(0, 4, size=int(rng.integers(2, 7))).astype(np.uint8), read[at:]])
+    read = read[:qhi]
+    if read.size == 0:
+        read = G[pos:pos + 1].copy()
+    lo = pos - int(rng.integers(0, min(40, 257 - ql) if fit else 40))
+    t = G[lo:lo + max(1, min(256, ql + int(rng.integers(0 if fit else -50, 51)) + (pos - lo)))].copy()
+    if rng.random() < 0.3:
+        read = (3 - read)[::-1].astype(np.uint8)
+        t = (3 - t)[::-1].astype(np.uint8)
+    return read.astype(np.uint8), t.astype(np.uint8)
+
+
+def _short_xtra(qlen, a, min_seed_len=19):
+    """mem_chain2aln_short's flags (software/bwamem.c:835)"""
+    return X_SUBO | X_START | (X_BYTE if qlen * a < 250 else 0) | (min_seed_len * a)
+
+
+def kswa_oins0(G, seed, a):
+    """o_ins = 0 (bwa mem -O o,0): the lazy-F loop ends at its first step, so F
+    crosses a block boundary into one column only.  Reads with 4 % indels and
+    two longer insertions each."""
+    rng = np.random.default_rng(seed)
+    items = []
+    for _ in range(600):
+        q, t = _short_pair(G, rng, 60, 199, float(rng.choice([0.0, 0.01, 0.03])), 0.04, n_runs=2)
+        items.append((q, t, _short_xtra(q.size, a)))
+    return _kswa_batch(items, a, 4 * a, 6 * a, a, 0, a)
+
+
+def kswa_xstop(G, seed):
+    """KSW_XSTOP | v in the caller's xtra: the forward pass ends at the first
+    row whose maximum reaches v.  v in {20, 40, 100} with and without XSUBO
+    (v is then the suboptimal threshold too) and XSTART, byte and 16-bit."""
+    rng = np.random.default_rng(seed)
+    items = []
+    for k in range(600):
+        q, t = _short_pair(G, rng, 60, 199, float(rng.choice([0.0, 0.01, 0.03])), float(rng.choice([0.0, 0.01])))
+        xtra = X_STOP | (20, 40, 100)[k % 3] | (X_SUBO if k // 3 % 2 else 0) | (X_START if k // 6 % 2 else 0) | \
+            (X_BYTE if k // 12 % 2 else 0)
+        items.append((q, t, xtra))
+    return _kswa_batch(items, 1, 4, 6, 1, 6, 1)
+
+
+def kswa_long(G, seed):
+    """queries of 200..256 bp (the fourth 64-column chunk of the wave), 16-bit"""
+    rng = np.random.default_rng(seed)
+    items = []
+    for _ in range(500):
+        q, t = _short_pair(G, rng, 200, 256, float(rng.choice([0.0, 0.01, 0.03, 0.06])),
+                           float(rng.choice([0.0, 0.005, 0.02])), fit=rng.random() < 0.5, exact=True)
+        if rng.random() < 0.15:
+            q[rng.random(q.size) < 0.02] = 4
+        items.append((q, t, X_SUBO | X_START | 19))
+    return _kswa_batch(items, 1, 4, 6, 1, 6, 1)
+
+
+EDGE_QLEN = [1, 7, 8, 9, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256]
+EDGE_TLEN = [0, 1, 63, 64, 65, 255, 256]
+
+
+def kswa_edge(seed, byte):
+    """every query length around a multiple of the vector width (8 and 16) and
+    of the wave's 64-column chunk against every target length around the
+    chunk, as a matching, a 10 %-mutated and an all-N query; the byte set adds
+    the longest suboptimal list: `A` (and `AC`) against (AC)^128 with a
+    threshold of 1 lists every second row, 128 entries"""
+    rng = np.random.default_rng(seed)
+    items = []
+    for qlen in EDGE_QLEN:
+        for tlen in EDGE_TLEN:
+            for kind in range(3):
+                q = rng.integers(0, 4, size=qlen).astype(np.uint8)
+                if tlen >= qlen:
+                    off = int(rng.integers(0, tlen - qlen + 1))
+                    t = np.concatenate([rng.integers(0, 4, size=off), q, rng.integers(0, 4, size=tlen - qlen - off)])
+                else:
+                    off = int(rng.integers(0, qlen - tlen + 1))
+                    t = q[off:off + tlen].copy()
+                if kind == 1:
+                    m = synth._mutated_copy(q, rng, 0.08, 0.02)
+                    q = np.concatenate([m, rng.integers(0, 4, size=qlen)]).astype(np.uint8)[:qlen]
+                elif kind == 2:
+                    q[:] = 4
+                items.append((q, t.astype(np.uint8), X_SUBO | X_START | (X_BYTE if byte else 0) | 19))
+    if byte:
+        ac = np.tile(np.array([0, 1], np.uint8), 128)
+        items.append((ac[:1].copy(), ac, X_SUBO | X_START | X_BYTE | 1))
+        items.append((ac[:2].copy(), ac, X_SUBO | X_START | X_BYTE | 1))
+    return _kswa_batch(items, 1, 4, 6, 1, 6, 1)
+
+
+def kswa_sat(G, seed, a):
+    """byte scores at the ceiling: ksw_u8 stops at gmax + shift >= 255 and
+    returns score 255, qe -1.  Clean and lightly mutated reads whose full match
+    scores 220..256: at a = 2 (bias 8) 110..124 bp, at a = 1 (bias 4) 245..256
+    bp with KSW_XBYTE forced"""
+    rng = np.random.default_rng(seed)
+    lo, hi = (110, 124) if a == 2 else (245, 256)
+    items = []
+    for k in range(400):
+        ql = int(rng.integers(lo, hi + 1)) if k % 2 else int(rng.integers(hi - 2, hi + 1))
+        sub = float(rng.choice([0.0, 0.0, 0.0, 0.01]))
+        q, t = _short_pair(G, rng, ql, ql, sub, 0.0, fit=True)
+        items.append((q, t[:256], X_SUBO | X_START | X_BYTE | 19 * a))
+    return _kswa_batch(items, a, 4 * a, 6 * a, a, 6 * a, a)
+
+
+def kswa_gaps(G, seed, o_del, e_del, o_ins, e_ins):
+    """the make_kswa_tasks mix under other gap penalties"""
+    kb = synth.make_kswa_tasks(G, 300, seed=seed)
+    kb.o_del, kb.e_del, kb.o_ins, kb.e_ins = o_del, e_del, o_ins, e_ins
+    return kb
+
+
+# the sets that go past kswa_a1 / kswa_a2: o_ins = 0, asymmetric gaps and
+# o_del = 0, KSW_XSTOP, 200-256 bp, the length edges, byte saturation
+KSWA_MORE = [
+    ("kswa_oins0", lambda G: kswa_oins0(G, 161, 1)),
+    ("kswa_oins0_a2", lambda G: kswa_oins0(G, 162, 2)),
+    ("kswa_asym", lambda G: kswa_gaps(G, 163, 5, 3, 8, 1)),
+    ("kswa_odel0", lambda G: kswa_gaps(G, 164, 0, 2, 8, 1)),
+    ("kswa_xstop", lambda G: kswa_xstop(G, 165)),
+    ("kswa_long", lambda G: kswa_long(G, 166)),
+    ("kswa_edge_b", lambda G: kswa_edge(167, True)),
+    ("kswa_edge_w", lambda G: kswa_edge(168, False)),
+    ("kswa_sat", lambda G: kswa_sat(G, 169, 2)),
+    ("kswa_sat_a1", lambda G: kswa_sat(G, 170, 1)),
+]
 
 
 def make_kswa():
@@ -286,8 +475,11 @@ def make_kswa():
         with gzip.open(os.path.join(HERE, "g1.fa.gz"), "rb") as fh:
             from tests import golden_data
             g = golden_data.fasta_codes(fh.read())
-        for name, a, b, o, e, seed in KSWA_SETS:
-            kb = synth.make_kswa_tasks(g, 3000, seed=seed, a=a, b=b, o=o, e=e)
+        sets = [(name, lambda G, s=(seed, a, b, o, e): synth.make_kswa_tasks(G, 3000, seed=s[0], a=s[1], b=s[2], o=s[3],
+                                                                             e=s[4]))
+                for name, a, b, o, e, seed in KSWA_SETS] + KSWA_MORE
+        for name, make in sets:
+            kb = make(g)
             p = os.path.join(tmp, name + ".smat")
             synth.write_smat(p, kb)
             oracle.ref_kswa(p, os.path.join(tmp, name + ".smar"))
@@ -354,6 +546,8 @@ if __name__ == "__main__":
     elif "--ksw-only" in sys.argv:
         make_ksw()
         make_aln()
+    elif "--ksw-gap0-only" in sys.argv:
+        make_ksw_gap0()
     elif "--kswa-only" in sys.argv:
         make_kswa()
     elif "--chains-only" in sys.argv:

@@ -210,6 +210,72 @@ def test_aln_gpu_vs_oracle_repeat_dense(gpu_device, w, a, heavy, monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("o_del,o_ins", [(6, 0), (0, 0)], ids=["o_ins0", "o_del0_o_ins0"])
+def test_aln_gpu_vs_oracle_gap_open_0(gpu_device, o_del, o_ins):
+    """Gap open 0 (bwa mem -O 6,0 and -O 0,0): with o_ins = 0 the reference's
+    ksw_align2 carries F across a block of its striped query into one column
+    only (tests/test_ksw_align.py), and the regions go into SAM as they are.
+    200 kbp, 1000 reads with 3 % indels and one longer insertion each, half
+    150 bp and half 257..500 bp, and 500 reads whose only match is a stretch of
+    45..95 bp between unrelated flanks: a chain that short inside a read is what
+    mem_chain2aln_short takes (software/bwamem.c:825-836).  GPU regions ==
+    restatement on all three routes of test_aln_gpu_vs_oracle_repeat_dense."""
+    import smemgpu
+    from smemgpu import synth
+    g = synth.make_genome(200_000, seed=96, repeat_frac=0.6, n_families=5, exact_frac=0.01, tandem_frac=0.01)
+    idx, sa = smemgpu.Index.build_sa(g.codes, sa_intv=32)
+    src = synth.concat_reads([synth.make_reads(g.codes, 500, 150, seed=97, sub_rate=0.02),
+                              synth.make_reads(g.codes, 500, (257, 500), seed=98, sub_rate=0.02)])
+    rng = np.random.default_rng(99)
+    parts = []
+    for i in range(src.n):
+        r = synth._mutated_copy(src.read(i), rng, 0.0, 0.03)
+        at = int(rng.integers(1, r.size))
+        parts.append(np.concatenate([r[:at], rng.integers(0, 4, size=int(rng.integers(2, 7))).astype(np.uint8),
+                                     r[at:]]))
+    for i in range(500):
+        n = int(rng.integers(45, 96))
+        pos = int(rng.integers(0, g.codes.size - n))
+        r = synth._mutated_copy(g.codes[pos:pos + n], rng, 0.01, 0.03)
+        at = int(rng.integers(r.size // 4, 3 * r.size // 4))
+        r = np.concatenate([r[:at], rng.integers(0, 4, size=int(rng.integers(2, 7))).astype(np.uint8), r[at:]])
+        if i % 2:
+            r = (3 - r)[::-1]
+        parts.append(np.concatenate([rng.integers(0, 4, size=int(rng.integers(70, 200))), r,
+                                     rng.integers(0, 4, size=int(rng.integers(70, 200)))]).astype(np.uint8))
+    lens = np.array([p.size for p in parts], dtype=np.int32)
+    reads = synth.Reads(lens, np.concatenate(parts).astype(np.uint8),
+                        np.concatenate([[0], np.cumsum(lens, dtype=np.int64)]))
+    opt = oracle.aln_opt(o_del=o_del, o_ins=o_ins)
+    pac = _pack(g.codes)
+    l_pac = int(g.codes.size)
+    gpu = smemgpu.Gpu(idx, device=gpu_device)
+    try:
+        gpu.load_sa(sa)
+        gpu.load_pac(pac, l_pac)
+        b = gpu.batch(reads.n, reads.codes.size, int(reads.lens.max()))
+        try:
+            b.set_reads(reads.codes, reads.offs)
+            b.run(smemgpu.Options())
+            b.sa(19, 10000)
+            b.chain(l_pac)
+            b.chain2aln(opt)
+            res = b.fetch()
+            chains, chain_off, seeds = res.chains, res.chain_off, res.seeds
+        finally:
+            b.close()
+        raw, off, ms = gpu.chain2aln(pac, l_pac, reads.codes, reads.offs, chains, chain_off, seeds, opt)
+        raw2, off2, _ = gpu.chain2aln(None, l_pac, reads.codes, reads.offs, chains, chain_off, seeds, opt)
+    finally:
+        gpu.close()
+    want, want_off = oracle.aln(pac, l_pac, reads.codes, reads.offs, chains, chain_off, seeds, opt)
+    assert want.size > 500
+    for r, o in ((raw, off), (raw2, off2), (res.regs, res.reg_off)):
+        got = np.frombuffer(r.tobytes(), dtype=golden_data.ALNREG_DT)
+        _assert_same(got, o, want, want_off)
+
+
+@pytest.mark.gpu
 def test_aln_gpu_argument_checks(gpu_device):
     """The host API refuses query codes > 4 (they would index past the scoring
     matrix), chains sharing seeds (they would share sort scratch), a short

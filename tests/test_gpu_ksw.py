@@ -51,7 +51,16 @@ def test_ksw_golden_fixture(gpu):
     assert np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("scoring", ["bwa", "a2b3", "asym"])
+def test_ksw_golden_fixture_gap0(gpu):
+    """both gap opens 0, the compiled reference's results (tests/golden/ksw_gap0.*)"""
+    from smemgpu import synth
+    b = synth.read_smkt(golden_data.gz("ksw_gap0.smkt.gz"))
+    want = synth.read_smkr(golden_data.gz("ksw_gap0.smkr.gz"))
+    got, _ = gpu.ksw_extend(b)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("scoring", ["bwa", "a2b3", "asym", "gap0"])
 def test_ksw_vs_oracle(gpu, scoring):
     from smemgpu import synth
     g = synth.make_genome(400_000, seed=142, n_chrom=1)
@@ -61,6 +70,8 @@ def test_ksw_vs_oracle(gpu, scoring):
     elif scoring == "asym":
         b.mat = synth.bwa_scmat(1, 4)
         b.o_del, b.e_del, b.o_ins, b.e_ins = 5, 3, 8, 1
+    elif scoring == "gap0":
+        b.o_del, b.e_del, b.o_ins, b.e_ins = 0, 1, 0, 1
     got, ms = gpu.ksw_extend(b)
     want = oracle.ksw(b)
     bad = np.nonzero(got != want)[0]

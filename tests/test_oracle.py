@@ -251,6 +251,18 @@ def test_ksw_oracle_matches_reference_golden():
     assert np.array_equal(oracle.ksw(b), want)
 
 
+def test_ksw_oracle_matches_reference_gap0():
+    """The same with both gap opens 0 (e = 1), 500 problems: a gap then costs
+    what its extension costs, and E and F tie with H - oe at every cell."""
+    from smemgpu import synth
+    from tests import golden_data
+    b = synth.read_smkt(golden_data.gz("ksw_gap0.smkt.gz"))
+    want = synth.read_smkr(golden_data.gz("ksw_gap0.smkr.gz"))
+    assert b.tasks.size == want.size == 500
+    assert (b.o_del, b.e_del, b.o_ins, b.e_ins) == (0, 1, 0, 1)
+    assert np.array_equal(oracle.ksw(b), want)
+
+
 def test_ksw_oracle_matches_reference_live(tmp_path):
     """Fresh problems under other scoring (a=2 b=3, o_del 5 e_del 2, o_ins 4
     e_ins 1), checked against the reference binary when it is built."""
