@@ -4,8 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define SMEM_OVERFLOW 0xFFFFFFFFu
-
 namespace smem {
 
 // bwtintv_t (software/bwt.h:60-62)
@@ -13,12 +11,17 @@ struct Intv {
     uint64_t x0, x1, x2, info;
 };
 
-// One smem_next2 call as the seeding kernel logs it: the call's raw region
-// holds m_n matches then s_n sub-matches, each in the order bwt_smem1 pushed
-// them (the reverse of their final order); max_len is the longest match.
-struct CallRec {
-    uint32_t m_n, s_n, ori_start, max_len;
-};
+// A raw log record is a bwtintv_t whose x0 word also carries, above the 34-bit
+// coordinate, where the record belongs in the read's output: bits 34-62 the
+// ordinal of its smem_next2 call within the read (one call per base at most,
+// reads <= 2^24 bases), bit 63 set for a sub-match of the call's re-seeding
+// pass.  A call's records are contiguous: its matches, then the sub-matches
+// the merge keeps, each run in the order bwt_smem1 pushed it (the reverse of
+// its final order).  x1, x2 and info are bwtintv_t's.
+constexpr int RAW_ORD_SHIFT = 34;
+constexpr uint64_t RAW_COORD_MASK = (1ull << RAW_ORD_SHIFT) - 1;
+constexpr uint32_t RAW_ORD_MASK = (1u << 29) - 1;   // of x0 >> RAW_ORD_SHIFT
+constexpr uint32_t RAW_SUB_BIT = 1u << 29;          // of x0 >> RAW_ORD_SHIFT
 
 struct SeedParams {
     const uint32_t* bwt;       // interleaved BWT + Occ, resident in HBM (reference layout)
@@ -31,14 +34,12 @@ struct SeedParams {
     const int32_t* read_ids;   // work item -> read (nullptr: identity)
     int n_items;
     int min_seed_len, split_len_init, split_width, start_width;
-    Intv* out_intv;            // raw lists [item][cap_intv]
-    uint32_t cap_intv;
-    CallRec* out_call;         // [item][cap_calls]
-    uint32_t cap_calls;
-    uint32_t* n_intv;          // [item] raw intervals, or SMEM_OVERFLOW
-    uint32_t* n_calls;         // [item]
-    uint64_t* s_intv;          // [read] intervals smem_next2 returns for the read (compaction sizes)
-    uint64_t* s_calls;         // [read] smem_next2 lists of the read
+    Intv* out_intv;            // raw logs [item][slot_intv], 64-B aligned
+    uint32_t cap_intv;         // records a read may log; one more sends it to the overflow pass
+    uint32_t slot_intv;        // cap_intv rounded up to even: record pairs are whole 64-B lines
+    uint64_t* sizes;           // [read][2] intervals, smem_next2 lists of the read (one 16-B store;
+                               // the compaction scans read it with stride 2); not written for a
+                               // read that overflowed
     int32_t* ovf_count;
     int32_t* ovf_items;
     int32_t* head;             // work counter, zeroed before each launch
@@ -73,19 +74,12 @@ struct SaParams {
 struct FinalizeParams {
     int n;
     const uint64_t* offs;          // read lengths for the merge key
-    const uint32_t* n_intv;
-    const uint32_t* n_calls;
+    const uint64_t* sizes;         // [read][2] intervals (= raw records), lists
     const Intv* main_intv;
-    const CallRec* main_call;
-    uint32_t cap_intv, cap_calls;
-    const int32_t* ovf_slot;
+    uint32_t slot_intv;            // records per read slot
+    const int32_t* ovf_slot;       // [read] slot in ovf_intv, -1: main; nullptr: no read overflowed
     const Intv* ovf_intv;
-    const CallRec* ovf_call;
-    const uint32_t* ovf_n_calls;
-    uint32_t ovf_cap_intv, ovf_cap_calls;
-    // count pass writes sizes; write pass reads offsets and writes flat outputs
-    uint64_t* s_intv;
-    uint64_t* s_calls;
+    uint32_t ovf_slot_intv;
     const uint64_t* intv_off;
     const uint64_t* call_off;
     Intv* flat_intv;
@@ -120,4 +114,7 @@ hipError_t smem_launch_sa_densify2(const smem::SaParams* S, uint32_t dshift, uin
 hipError_t smem_launch_sa_walk(const smem::SaParams* S, int grid, hipStream_t st);
 hipError_t smem_launch_offsets(const uint64_t* in, uint64_t* out, int n, void* temp, size_t* temp_bytes,
                                hipStream_t st);
+// the same over in[0], in[stride], ...; total != nullptr also receives out[n]
+hipError_t smem_launch_offsets_strided(const uint64_t* in, int stride, uint64_t* out, int n, void* temp,
+                                       size_t* temp_bytes, uint64_t* total, hipStream_t st);
 }

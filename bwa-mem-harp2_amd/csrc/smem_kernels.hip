@@ -455,24 +455,6 @@ __device__ __forceinline__ void next_offsets(const SeedParams& P, int it, uint32
     len = (int)(b - a);
 }
 
-// a raw output record (Intv 32 B / CallRec 16 B), non-temporal when NT
-template <bool NT, class T>
-__device__ __forceinline__ void put_rec(T* p, const T& v) {
-    static_assert(sizeof(T) % 16 == 0, "16-B records");
-    if constexpr (NT) {
-        const uint4* s = reinterpret_cast<const uint4*>(&v);
-        nt_v4u* d = reinterpret_cast<nt_v4u*>(p);
-#pragma unroll
-        for (int k = 0; k < (int)(sizeof(T) / 16); ++k) {
-            nt_v4u w;
-            w.x = s[k].x, w.y = s[k].y, w.z = s[k].z, w.w = s[k].w;
-            __builtin_nontemporal_store(w, d + k);
-        }
-    } else {
-        *p = v;
-    }
-}
-
 // chip-wide 100 MHz clock: wave start / end times comparable across XCDs
 __device__ __forceinline__ uint64_t rtstamp() {
     uint64_t t;
@@ -484,799 +466,6 @@ __device__ __forceinline__ uint64_t stamp() {
     uint64_t t;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
     return t;
-}
-
-// STAMP: diagnostic build only (variant 9) — per-wave cycle split written to P.dbg_buf
-// FRING: the forward list goes to the LDS list slots too, as a ring of the
-// last NLIST pushes (an older entry is written to the arena when the ring
-// wraps), so that the first backward step reads prev[0 .. NLIST) from LDS and
-// only longer forward lists touch HBM.  List index k < NLIST of every list of
-// one bwt_smem1 call then lives in slot (R - k) mod NLIST, R = the slot of the
-// last forward push (prev[0]): curr[k] still overwrites prev[k] only after it
-// was read.
-// DUAL: a lane in a backward step with two or more entries left extends
-// prev[j] and prev[j+1] in the same iteration (the entries of one step are
-// independent, software/bwt.c:812-826) and consumes both results in order
-// next iteration: half the iterations -- state-machine passes and memory
-// round trips -- for the multi-entry steps.  The second extend's buckets
-// come from the lane's LDS slots when the first fetched them, else straight
-// into registers.
-// VSLOT: the two bucket slots per lane in registers instead of LDS (4 KB of
-// LDS per wave back for list entries); with DUAL the second extend is issued
-// only when both its buckets are in the slots after the first one's fetch.
-// KT: an extend whose result is a string of at most P.kt_k bases reads that
-// string's bi-interval from the k-mer table (one 16-B probe, no rank) instead
-// of two Occ buckets: a bi-interval is a function of the string alone, so the
-// result is the one bwt_extend computes.  The lane keeps the 2-bit codes of
-// its forward string (first kt_k bases) and, in the backward phase, of the
-// kt_k bases from the current position (rolled one base per step).
-// PRIO (A/B): wave priority by phase -- 1: raised from the top of an
-// iteration (the advance) until its loads are issued, 2: raised for the
-// extend arithmetic after the wait (s_setprio; the SQ's arbitration between
-// the three waves of a SIMD)
-// NTM (A/B, bits): 1 the Occ bucket loads non-temporal; 2 the raw outputs
-// (intervals, list records) stored non-temporal -- finalize_kernel reads them
-// once, later, so they need not occupy L2 beside the list arena
-template <int FETCH, bool STAMP, int WPE, int NLIST, bool SINGLE = true, bool EARLY = false, bool L192 = false,
-          bool FRING = false, bool DUAL = false, bool VSLOT = false, bool KTAB = false, bool PFCH = false, int PRIO = 0,
-          int NTM = 0>
-__global__ __launch_bounds__(256, WPE) void seed_kernel(SeedParams P) {
-    // backward lists: the first NLIST entries live in LDS
-    constexpr int NL = NLIST;
-    constexpr bool VS = VSLOT && FETCH == FETCH_OCC64 && !EARLY;
-    constexpr bool KT = KTAB && VS && !DUAL;
-    using WaveLds = WaveLdsT<VS ? 0 : (FETCH == FETCH_OCC64 ? 4 : 8)>;
-    __shared__ WaveLds lds[4];  // one per wave of the 256-thread block
-    __shared__ WaveListT<NL> lists[4];
-    __shared__ uint32_t scnt[STAMP ? 4 : 1][16];  // STAMP: per-wave block-execution counts
-    if constexpr (STAMP) {
-        if ((threadIdx.x & 63) < 16) scnt[threadIdx.x >> 6][threadIdx.x & 63] = 0;
-    }
-    const int lane = threadIdx.x & 63;
-    WaveLds* W = &lds[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
-    WaveListT<NL>* WLs = &lists[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
-    const uint64_t lane_g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t cap = P.cap_list;
-    // per-lane scratch: two packed lists (B0 | B1) used as forward / prev / curr
-    PIntv* __restrict__ bp = reinterpret_cast<PIntv*>(P.scratch + lane_g * 2ull * cap);
-
-    // All loads the state machine needs are issued in the uniform section
-    // below, next to the bucket DMAs, and consumed in the following
-    // iteration: a load consumed inside the divergent advance would stall
-    // the whole wave for one memory round trip.  A lane whose next step needs
-    // data that is not in flight yet "yields" one iteration instead.
-    int phase = P_FETCH;
-    int item = -1, len = 0;
-    int nitem = 0, nlen = -2;  // next read: -2 nothing claimed, -1 claimed, >= 0 offsets loaded
-    int rid = 0, nrid = 0;     // read index of the item (overflow pass: through read_ids)
-    // PFCH: the next read's claim and loads are issued in the uniform section
-    // beside the bucket loads and consumed at the top of the next iteration,
-    // so no wave ever waits on them (the blocking claim at the top stalled
-    // the whole wave for two memory round trips in ~12 % of iterations,
-    // profiles/r03/stamps): nst walks NST_CLAIM -> NST_CLAIMING -> (overflow
-    // pass: NST_RID -> NST_RIDING) -> NST_OFF -> NST_OFFING -> NST_READY, and
-    // a lane takes its next read the iteration after it finished one.
-    enum { NST_CLAIM = 0, NST_CLAIMING, NST_RID, NST_RIDING, NST_OFF, NST_OFFING, NST_READY };
-    int nst = NST_CLAIM;
-    int natom = 0, nrank = 0;      // the wave's claim (leader lane's atomic return), this lane's rank in it
-    int nridv = 0;                 // overflow pass: read_ids[nitem] in flight
-    uint32_t clead = 0;            // the claim's leader lane (wave-uniform)
-    uint4 noffv = {0, 0, 0, 0};    // offs[rid], offs[rid + 1] in flight
-    uint32_t keep_n = 0;       // intervals of the read that smem_next2 returns (matches + kept sub-matches)
-    uint32_t o0 = 0, no0 = 0;
-    uint32_t qb = ~0u, qwant = ~0u;      // 16-B query window held / wanted (offsets into codes)
-    uint4 qv = {0, 0, 0, 0};
-    uint32_t raw_n = 0, calls_n = 0;     // raw intervals / lists logged for the read
-    int start = 0, ori_start = 0;
-    int x = 0, min_intv = 1, middle = 0, i = 0, j = 0, ret = 0, cur_c = 0;
-    uint64_t ik0 = 0, ik1 = 0, ik2 = 0;
-    uint32_t ikend = 0;
-    // per-lane arena: [0, cap) the forward list (pushed downward, so ascending
-    // order is the reversed list bwt_smem1 iterates), [cap, 2 cap) the backward
-    // list beyond its first NL entries (which live in LDS).  curr is written in
-    // place over prev: curr[k] is pushed after prev[j >= k] has been read.
-    uint32_t fwd_n = 0, prev_off = 0, prev_n = 0, curr_n = 0;
-    // FRING: the ring position (forward phase), then the slot of list index 0
-    uint32_t lr = 0;
-    constexpr bool RING = FRING && NL > 0;
-    constexpr bool DU = DUAL && RING && NL > 1 && FETCH == FETCH_OCC64 && !EARLY && !L192;
-    bool dq = false;                    // DU: the lane's request covers prev[j] and prev[j + 1]
-    uint4 pn2 = {0, 0, 0, 0};           // DU: prev[j + 1] for the next request
-    uint4 ent2 = {0, 0, 0, 0};          // DU: the second entry of the current request
-    uint64_t na2 = 0, nb2 = 0, ns2 = 0; // DU: its result
-    uint4 s0a = {0, 0, 0, 0}, s0b = {0, 0, 0, 0}, s1a = {0, 0, 0, 0}, s1b = {0, 0, 0, 0};  // VS: the slots
-    // KT: codes of the forward string (its first K bases), of the requested
-    // forward string, and of the K bases from backward position i
-    uint32_t kc = 0, kreq = 0, kb = 0;
-    const int K = KT ? P.kt_k : 0;
-    bool prev_lds = false;  // prev is the backward list (LDS + region 2), not the forward list
-    uint32_t mem_n = 0, mem_last_start = 0, m_n = 0;
-    uint64_t curr_last_x2 = 0;
-    // longest match of the first bwt_smem1 (software/bwamem.c:266-270), tracked
-    // as matches are emitted: pushes come in reverse final order, so ">="
-    // keeps the first maximum in final order
-    uint32_t max_len = 0, max_x2 = 0, max_mid = 0;  // x2 saturated to 32 bits
-    uint4 pn = {0, 0, 0, 0}, head = {0, 0, 0, 0};  // prev[j+1] in flight, curr[0]
-    uint64_t na = 0, nb = 0, ns = 0;
-    uint32_t tag0 = ~0u, tag1 = ~0u;  // FETCH_OCC64: buckets held in the lane's two LDS slots
-    // wave-cooperative backward step (tail of the batch): idle lanes extend
-    // entries of owner lanes' prev lists
-    int bat_m = 0;        // this lane's helped entries for its next BWD_RES (owner only)
-    uint64_t bat_h = 0;   // the lanes that computed them, in entry order
-    uint64_t st_adv = 0, st_fetch = 0, st_comp = 0, st_iter = 0, st_active = 0, st_t0 = 0, st_t1 = 0;
-    if constexpr (STAMP) st_t0 = rtstamp();
-    // the launch's span on the chip clock: first wave start, last wave end
-    if (P.tspan && lane == 0) atomicMax(reinterpret_cast<unsigned long long*>(P.tspan), ~(unsigned long long)rtstamp());
-
-#define QBLK(pos) ((o0 + (uint32_t)(pos)) & ~15u)
-// one forward-list push: the arena (pushed downward: ascending order is the
-// reversed list) or, RING, the LDS ring, spilling the entry it displaces
-#define FWD_PUSH(e_)                                                                        \
-    {                                                                                       \
-        const uint4 fe_ = (e_);                                                             \
-        if constexpr (RING) {                                                               \
-            if (fwd_n >= (uint32_t)NL)                                                      \
-                *reinterpret_cast<uint4*>(bp + cap - 1 - (fwd_n - NL)) = WLs->e[lr][vlane()]; \
-            WLs->e[lr][vlane()] = fe_;                                                      \
-            lr = lr + 1 == (uint32_t)NL ? 0u : lr + 1;                                      \
-        } else {                                                                            \
-            *reinterpret_cast<uint4*>(bp + cap - 1 - fwd_n) = fe_;                          \
-        }                                                                                   \
-        ++fwd_n;                                                                            \
-    }
-// the LDS slot of list index k (< NL) of the current bwt_smem1 call
-#define LSLOT(r_, k_) (RING ? ((r_) >= (k_) ? (r_) - (k_) : (r_) + (uint32_t)NL - (k_)) : (k_))
-#define YIELD_FOR(pos)            \
-    {                             \
-        qwant = QBLK(pos);        \
-        break;                    \
-    }
-
-    for (;;) {
-        uint64_t ta = 0;
-        if constexpr (STAMP) ta = stamp();
-        if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(2);
-        // claiming the next read and loading its offsets: here, at the top of the
-        // iteration, where no bucket DMA is in flight yet for their waits to cover
-        if constexpr (PFCH) {
-            // what the last iteration's uniform section issued has landed
-            // (its vmcnt(0) wait): consume it, issue nothing here
-            if (nst == NST_CLAIMING) {
-                nitem = __builtin_amdgcn_readlane(natom, clead) + nrank;
-                nst = nitem >= P.n_items ? NST_READY : (P.read_ids ? NST_RID : NST_OFF);
-                nrid = nitem;
-            } else if (nst == NST_RIDING) {
-                nrid = nridv;
-                nst = NST_OFF;
-            } else if (nst == NST_OFFING) {
-                no0 = noffv.x;
-                nlen = (int)(noffv.z - noffv.x);
-                nst = NST_READY;
-            }
-        } else if (phase == P_FETCH) {
-            if (nlen == -2) {  // claim the next read
-                nitem = atomicAdd(P.head, 1);
-                nlen = -1;
-            } else if (nlen == -1) {  // its offsets (the claim returned last iteration)
-                next_offsets(P, nitem, no0, nlen, nrid);
-            }
-        }
-        // ---- advance the state machine until the lane needs an extend ----
-        // Blocks are laid out in the order the common transitions take, and a
-        // block hands over to a LATER block by setting `phase` and falling
-        // through: result -> next forward base, forward stop -> list reversal
-        // -> first backward step, end of a backward step -> next step all
-        // complete in one pass of the wave.  Going back to an earlier block
-        // (end of a bwt_smem1 call, next read) takes another pass.  A lane sets
-        // `out` when it has an extend request (or yields); the pass has a
-        // single exit at the bottom, which keeps the exec-mask bookkeeping of
-        // the structurized loop (and so the register count) small.
-        // ONE pass per iteration (SINGLE): a lane that still needs an earlier
-        // block after this pass (end of a bwt_smem1 call: ~1 % of lane-
-        // iterations) continues next iteration without an extend, instead of
-        // the whole wave running a second pass.
-        bool out = false;
-        bool early = false;  // FETCH_OCC64: this lane's bucket fetch was issued in BWD_RES
-        int fks = -1, fls = -1;  // its bucket slots
-        for (int pass = 0; phase != P_EXIT && (pass == 0 || !SINGLE); ++pass) {
-            if constexpr (STAMP) {  // which blocks this pass of the wave starts in (any lane)
-                const uint64_t act = __ballot(1);
-                uint32_t any = 0;
-                for (int ph = 0; ph < P_EXIT; ++ph) any |= (__ballot(phase == ph) ? 1u : 0u) << ph;
-                if (lane == __ffsll((unsigned long long)act) - 1) {
-                    scnt[threadIdx.x >> 6][15] += 1;
-                    for (int ph = 0; ph < P_EXIT; ++ph) scnt[threadIdx.x >> 6][ph] += (any >> ph) & 1;
-                }
-            }
-            out = false;
-            if (phase == P_SMEM_END) {
-                if (!middle) {  // software/bwamem.c:261-272
-                    start = ret;
-                    m_n = mem_n;
-                    // split_len = min(k * split_factor + .499, len) (software/bwamem.c:456-458)
-                    const int split_len = P.split_len_init < len ? P.split_len_init : len;
-                    if (m_n > 0 && split_len > 0 && (int)max_len >= split_len &&
-                        (uint64_t)max_x2 <= (uint64_t)(int64_t)P.split_width) {
-                        // re-seed from the middle of the longest SMEM (software/bwamem.c:272-278)
-                        x = (int)max_mid;
-                        min_intv = (int)(max_x2 + 1);
-                        middle = 1;
-                        phase = P_SMEM_BEGIN;
-                    }
-                }
-                if (phase == P_SMEM_END) {
-                    // log the list: matches (+ sub-matches) for the finalize pass
-                    if (calls_n >= P.cap_calls) {
-                        phase = P_OVF;
-                    } else {
-                        put_rec<(NTM & 2) != 0>(P.out_call + (uint64_t)item * P.cap_calls + calls_n++,
-                                                CallRec{m_n, middle ? mem_n : 0u, (uint32_t)ori_start, max_len});
-                        phase = P_NEXT2;
-                    }
-                }
-            }
-            if (phase == P_OVF) {  // the read does not fit: hand it to the overflow pass
-                P.n_intv[item] = SMEM_OVERFLOW;
-                P.n_calls[item] = 0;
-                const int slot = atomicAdd(P.ovf_count, 1);
-                P.ovf_items[slot] = item;
-                phase = P_FETCH;
-            }
-            if (phase == P_FETCH) {
-                // claiming the next read and loading its offsets happen in the
-                // uniform section; yield until both are done
-                if (PFCH ? nst != NST_READY : nlen < 0) {
-                    out = true;
-                } else if (nitem >= P.n_items) {
-                    phase = P_EXIT;
-                    out = true;
-                } else {
-                    item = nitem;
-                    rid = nrid;
-                    keep_n = 0;
-                    o0 = no0;
-                    len = nlen;
-                    nlen = -2;
-                    nst = NST_CLAIM;  // PFCH: the next claim goes out in this iteration's uniform section
-                    raw_n = 0;
-                    calls_n = 0;
-                    start = 0;
-                    if (len < P.min_seed_len) {  // mem_chain's guard (software/bwamem.c:600)
-                        P.n_intv[item] = 0;
-                        P.n_calls[item] = 0;
-                        P.s_intv[rid] = 0;
-                        P.s_calls[rid] = 0;
-                        out = true;  // stays in P_FETCH: the next claim is issued below
-                    } else {
-                        phase = P_NEXT2;
-                    }
-                }
-            }
-            if (phase == P_NEXT2) {  // software/bwamem.c:247-261
-                bool wait_q = false;
-                if (start < len && start >= 0) {
-                    for (;;) {  // skip ambiguous bases
-                        if (start >= len) break;
-                        if (QBLK(start) != qb) { wait_q = true; break; }
-                        if (qsel(o0, start, qv) <= 3) break;
-                        ++start;
-                    }
-                }
-                if (wait_q) {
-                    qwant = QBLK(start);
-                    out = true;
-                } else if (start >= len || start < 0) {  // iterator exhausted
-                    P.n_intv[item] = raw_n;
-                    P.n_calls[item] = calls_n;
-                    P.s_intv[rid] = keep_n;  // sizes for the compaction scan (no count pass)
-                    P.s_calls[rid] = calls_n;
-                    phase = P_FETCH;
-                } else {
-                    ori_start = start;
-                    x = ori_start;
-                    min_intv = P.start_width;
-                    middle = 0;
-                    max_len = 0;
-                    phase = P_SMEM_BEGIN;
-                }
-            }
-            if (phase == P_SMEM_BEGIN) {  // software/bwt.c:782-789
-                if (QBLK(x) != qb) {
-                    qwant = QBLK(x);
-                    out = true;
-                } else {
-                    mem_n = 0;
-                    const int qx = qsel(o0, x, qv);
-                    if (qx > 3) {
-                        ret = x + 1;
-                        phase = P_SMEM_END;
-                    } else {
-                        if (min_intv < 1) min_intv = 1;
-                        const uint64_t lq = sel4(qx, P.L2[0], P.L2[1], P.L2[2], P.L2[3]);
-                        const uint64_t lq1 = sel4(qx, P.L2[1], P.L2[2], P.L2[3], P.L2[4]);
-                        ik0 = lq + 1;
-                        ik2 = lq1 - lq;
-                        ik1 = sel4(qx, P.L2[3], P.L2[2], P.L2[1], P.L2[0]) + 1;
-                        ikend = (uint32_t)(x + 1);
-                        if constexpr (KT) kc = (uint32_t)qx;
-                        fwd_n = 0;
-                        lr = 0;
-                        i = x + 1;
-                        phase = P_FWD;
-                    }
-                }
-            }
-            if (phase == P_BWD_RES) {  // software/bwt.c:815-825; na = x[0], nb = x[1]
-                // the lane's own result for prev[j], then (helped owner only) the
-                // results idle lanes computed for prev[j+1 .. j+bat_m], in order
-                const int own = DU && dq ? 2 : 1;
-                const int nres = own + bat_m;
-                uint64_t hm = bat_h;
-                for (int r = 0; r < nres; ++r) {
-                    if (DU && r == 1 && own == 2) {  // the lane's own second result, prev[j + 1]
-                        ik0 = p_x0(ent2); ik1 = p_x1(ent2); ik2 = p_x2(ent2); ikend = p_end(ent2);
-                        na = na2; nb = nb2; ns = ns2;
-                    } else if (r > 0) {
-                        const int h = __builtin_ctzll(hm);
-                        hm &= hm - 1;
-                        const uint4 ent = W->pn[h], res = W->q[h];
-                        ik0 = p_x0(ent); ik1 = p_x1(ent); ik2 = p_x2(ent); ikend = p_end(ent);
-                        na = p_x0(res); nb = p_x1(res); ns = p_x2(res);
-                    }
-                    if (ns < (uint64_t)min_intv) {
-                        // only prev[0] can be kept, when nothing longer survived
-                        if (curr_n == 0 && (mem_n == 0 || (uint32_t)(i + 1) < mem_last_start)) {
-                            if (raw_n >= P.cap_intv) {
-                                phase = P_OVF;
-                                break;
-                            }
-                            const uint64_t info = (uint64_t)ikend | ((uint64_t)(i + 1) << 32);
-                            put_rec<(NTM & 2) != 0>(P.out_intv + (uint64_t)item * P.cap_intv + raw_n++, Intv{ik0, ik1, ik2, info});
-                            // the merge keeps a sub-match if it is at least half the longest
-                            // match and ends after the call's start (software/bwamem.c:284-292)
-                            keep_n += !middle || (ikend - (uint32_t)(i + 1) >= (max_len >> 1) && ikend > (uint32_t)ori_start);
-                            ++mem_n;
-                            mem_last_start = (uint32_t)(i + 1);
-                            if (!middle && ikend - (uint32_t)(i + 1) >= max_len) {
-                                max_len = ikend - (uint32_t)(i + 1);
-                                max_x2 = ik2 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ik2;
-                                max_mid = (ikend + (uint32_t)(i + 1)) >> 1;
-                            }
-                        }
-                    } else if (curr_n == 0 || ns != curr_last_x2) {
-                        const uint4 e = pack_p(na, nb, ns, ikend);
-                        if (NL > 0 && curr_n < (uint32_t)NL)
-                            WLs->e[LSLOT(lr, curr_n)][vlane()] = e;
-                        else
-                            *reinterpret_cast<uint4*>(bp + cap + curr_n) = e;
-                        if (curr_n == 0) head = e;  // prev[0] of the next step
-                        ++curr_n;
-                        curr_last_x2 = ns;
-                    }
-                    ++j;
-                }
-                if (phase == P_BWD_RES) {
-                    if ((uint32_t)j < prev_n) {  // extend prev[j] (read into pn last iteration) right away
-                        ik0 = p_x0(pn); ik1 = p_x1(pn); ik2 = p_x2(pn); ikend = p_end(pn);
-                        out = true;
-                        if constexpr (DU) {  // and prev[j + 1] (in pn2) with it
-                            dq = (uint32_t)j + 1 < prev_n;
-                            ent2 = pn2;
-                        }
-                        if constexpr (FETCH == FETCH_OCC64 && EARLY) {
-                            // issue its bucket fetch now: it overlaps the rest of the pass
-                            const uint64_t k = ik0 - 1, l = k + ik2;
-                            fetch_occ64_issue<WaveLds, L192>(L192 ? P.occ192 : P.occ64, W, k - (k >= P.primary), l - (l >= P.primary), tag0, tag1,
-                                              fks, fls);
-                            early = true;
-                        }
-                    } else if (curr_n == 0) {  // software/bwt.c:827
-                        phase = P_SMEM_END;
-                    } else {
-                        prev_off = cap;  // software/bwt.c:828: swap, next position
-                        prev_n = curr_n;
-                        prev_lds = true;
-                        pn = head;
-                        --i;
-                        phase = P_BWD_STEP;
-                    }
-                }
-            }
-            if (phase == P_FWD_RES) {  // software/bwt.c:795-799; na = x[1], nb = x[0]
-                bool stop = false;
-                if (ns != ik2) {
-                    FWD_PUSH(pack_p(ik0, ik1, ik2, ikend));
-                    stop = ns < (uint64_t)min_intv;
-                }
-                if (stop) {
-                    phase = P_FWD_DONE;
-                } else {
-                    ik0 = nb; ik1 = na; ik2 = ns;
-                    ikend = (uint32_t)(i + 1);
-                    if constexpr (KT) {
-                        if (i + 1 - x <= K) kc = kreq;  // saturates at the first K bases
-                    }
-                    ++i;
-                    phase = P_FWD;
-                }
-            }
-            if (phase == P_FWD) {  // software/bwt.c:791-803
-                bool push = true;
-                if (i < len) {
-                    if (QBLK(i) != qb) {
-                        qwant = QBLK(i);
-                        out = true;
-                        push = false;
-                    } else {
-                        const int qi = qsel(o0, i, qv);
-                        if (qi < 4) {
-                            cur_c = 3 - qi;
-                            if constexpr (KT) kreq = kc << 2 | (uint32_t)qi;
-                            if (i + 1 < len) qwant = QBLK(i + 1);
-                            phase = P_FWD_RES;  // -> extend (forward)
-                            out = true;
-                            push = false;
-                        }
-                    }
-                }
-                if (push) {  // ambiguous base, or end of query: push ik and stop
-                    FWD_PUSH(pack_p(ik0, ik1, ik2, ikend));
-                    phase = P_FWD_DONE;
-                }
-            }
-            if (phase == P_FWD_DONE) {  // software/bwt.c:805-808
-                // the last push becomes prev[0] after the reversal; it is always the
-                // current ik (the stop path pushes ik without advancing it)
-                pn = pack_p(ik0, ik1, ik2, ikend);
-                ret = (int)ikend;
-                prev_off = cap - fwd_n;  // pushed downward: ascending = reversed
-                prev_n = fwd_n;
-                prev_lds = RING;         // RING: prev[0 .. NL) in the LDS ring
-                if constexpr (RING) lr = lr == 0 ? (uint32_t)NL - 1 : lr - 1;  // slot of the last push
-                if constexpr (KT) {  // the K bases from x (those past the forward string are never read)
-                    const uint32_t lf = ikend - (uint32_t)x;
-                    kb = lf >= (uint32_t)K ? kc : kc << (2 * ((uint32_t)K - lf));
-                }
-                i = x - 1;
-                phase = P_BWD_STEP;
-            }
-            if (phase == P_BWD_STEP) {  // software/bwt.c:810-812; prev[0] is in pn
-                if (i >= 0 && QBLK(i) != qb) {
-                    qwant = QBLK(i);
-                    out = true;
-                } else {
-                    cur_c = i < 0 ? -1 : qsel(o0, i, qv);
-                    if (cur_c > 3) cur_c = -1;
-                    curr_n = 0;
-                    if (cur_c >= 0) {
-                        j = 0;
-                        ik0 = p_x0(pn); ik1 = p_x1(pn); ik2 = p_x2(pn); ikend = p_end(pn);
-                        if constexpr (KT) kb = (uint32_t)cur_c << (2 * (K - 1)) | kb >> 2;
-                        if (i > 0) qwant = QBLK(i - 1);  // the next step's base
-                        phase = P_BWD_RES;  // -> extend prev[0]; prev[1] is fetched meanwhile
-                        out = true;
-                        if constexpr (DU) {  // prev[1] is in its LDS slot (ring or last step's curr)
-                            dq = prev_n > 1;
-                            if (dq) ent2 = WLs->e[LSLOT(lr, 1u)][vlane()];
-                        }
-                    } else {
-                        // nothing extends: prev[0] is the only candidate
-                        phase = P_SMEM_END;
-                        if (mem_n == 0 || (uint32_t)(i + 1) < mem_last_start) {
-                            if (raw_n >= P.cap_intv) {
-                                phase = P_OVF;
-                            } else {
-                                const uint64_t info = (uint64_t)p_end(pn) | ((uint64_t)(i + 1) << 32);
-                                put_rec<(NTM & 2) != 0>(P.out_intv + (uint64_t)item * P.cap_intv + raw_n++,
-                                                        Intv{p_x0(pn), p_x1(pn), p_x2(pn), info});
-                                keep_n += !middle || (p_end(pn) - (uint32_t)(i + 1) >= (max_len >> 1) &&
-                                                      p_end(pn) > (uint32_t)ori_start);
-                                ++mem_n;
-                                mem_last_start = (uint32_t)(i + 1);
-                                if (!middle && p_end(pn) - (uint32_t)(i + 1) >= max_len) {
-                                    max_len = p_end(pn) - (uint32_t)(i + 1);
-                                    max_x2 = p_x2(pn) > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)p_x2(pn);
-                                    max_mid = (p_end(pn) + (uint32_t)(i + 1)) >> 1;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            if (out) break;
-        }
-#undef YIELD_FOR
-#undef QBLK
-        // ---- uniform section: every lane takes part in the cooperative
-        // bucket fetch; the loads for the next iteration are issued here ----
-        const bool live = phase != P_EXIT;
-        bool want = out && (phase == P_BWD_RES || phase == P_FWD_RES);  // an extend request
-        uint64_t tb = 0;
-        if constexpr (STAMP) {
-            tb = stamp();
-            st_adv += tb - ta;
-            st_iter += 1;
-            st_active += __popcll(__ballot(want));
-        }
-        if (!__any(live)) break;
-        // DU with VS: the second extend is kept only when both its buckets are
-        // the first extend's (no extra loads); otherwise prev[j + 1] waits for
-        // the next iteration.  Decided before the helpers and the prefetch
-        // index, which depend on it.
-        if constexpr (DU && VS) {
-            if (dq && phase == P_BWD_RES && out) {
-                const uint64_t k1 = ik0 - 1, l1 = k1 + ik2;
-                const uint32_t b1k = (uint32_t)((k1 - (k1 >= P.primary)) >> 6), b1l = (uint32_t)((l1 - (l1 >= P.primary)) >> 6);
-                const uint64_t k2 = p_x0(ent2) - 1, l2 = k2 + p_x2(ent2);
-                const uint32_t b2k = (uint32_t)((k2 - (k2 >= P.primary)) >> 6), b2l = (uint32_t)((l2 - (l2 >= P.primary)) >> 6);
-                dq = (b2k == b1k || b2k == b1l) && (b2l == b1k || b2l == b1l);
-            }
-        }
-        // Lanes that found the work queue empty help: when the wave has idle
-        // lanes and a lane in a backward step with more entries left, each idle
-        // lane extends one of those entries (same base, independent of each
-        // other, software/bwt.c:812-826) and leaves entry + result in its pn / q
-        // slots; the owner consumes them in order next iteration.  This cuts the
-        // dependent chain of the few repeat-rich reads left at the end.
-        bat_m = 0;
-        bat_h = 0;
-        bool helper = false;
-        uint4 hent = {0, 0, 0, 0};
-        int hc = 0;
-        if constexpr (FETCH == FETCH_OCC64) {
-            const uint64_t idle = __ballot(phase == P_EXIT);
-            if (idle) {
-                // owners in lane order take the idle lanes in rank order, each as
-                // many as it has entries left in its step
-                uint64_t elig = __ballot(phase == P_BWD_RES && (uint32_t)j + 1 + (DU && dq ? 1u : 0u) < prev_n);
-                const uint32_t nidle = (uint32_t)__popcll(idle);
-                const int me = vlane();
-                const uint32_t r = (uint32_t)__popcll(idle & ((1ull << me) - 1));
-                uint32_t base = 0, he = 0, hpoff = 0, hlr = 0;
-                int ho = -1, hplds = 0;
-                while (elig && base < nidle) {
-                    // o is wave-uniform: its state is read with v_readlane (valid
-                    // whatever the exec mask, unlike a shuffle from an inactive lane)
-                    const int o = __builtin_ctzll(elig);
-                    elig &= elig - 1;
-                    const uint32_t jo = __builtin_amdgcn_readlane((int)j, o);
-                    const uint32_t pno = __builtin_amdgcn_readlane((int)prev_n, o);
-                    const uint32_t poff_o = __builtin_amdgcn_readlane((int)prev_off, o);
-                    const int plds_o = __builtin_amdgcn_readlane((int)prev_lds, o);
-                    const int c_o = __builtin_amdgcn_readlane(cur_c, o);
-                    const uint32_t lr_o = RING ? __builtin_amdgcn_readlane((int)lr, o) : 0u;
-                    const uint32_t dq_o = DU ? (uint32_t)__builtin_amdgcn_readlane((int)dq, o) : 0u;
-                    const uint32_t m = min(nidle - base, pno - jo - 1 - dq_o);
-                    const bool mine = phase == P_EXIT && r >= base && r < base + m;
-                    if (mine) {
-                        ho = o;
-                        he = jo + 1 + dq_o + (r - base);
-                        hc = c_o;
-                        hpoff = poff_o;
-                        hplds = plds_o;
-                        hlr = lr_o;
-                    }
-                    const uint64_t hmask = __ballot(mine);
-                    if (me == o) {
-                        bat_m = (int)m;
-                        bat_h = hmask;
-                    }
-                    base += m;
-                }
-                helper = ho >= 0;
-                if (helper) {
-                    // the owner's list: its first NL entries in LDS (after the first
-                    // step), the rest in its arena; prev_off / prev_lds are per owner
-                    if (NL > 0 && hplds && he < (uint32_t)NL) {
-                        hent = WLs->e[LSLOT(hlr, he)][ho];
-                    } else {
-                        const PIntv* obp = reinterpret_cast<const PIntv*>(
-                            P.scratch + ((uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u) + ho) * 2ull * cap);
-                        // the entry into this (idle) lane's pn slot by LDS-DMA: no
-                        // VGPR-destination load on the main path
-                        __builtin_amdgcn_global_load_lds(obp + hpoff + he, LDS_PTR(&W->pn[0]), 16, 0, 0);
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        hent = W->pn[me];
-                    }
-                }
-            }
-        }
-        if constexpr (PFCH) {
-            // the next read's claim / loads, waited for by this iteration's
-            // vmcnt(0) below and consumed at the top of the next one
-            if (nst == NST_RID) {
-                nridv = P.read_ids[nitem];
-                nst = NST_RIDING;
-            } else if (nst == NST_OFF) {
-                const uint2* op = reinterpret_cast<const uint2*>(P.offs + nrid);
-                const uint2 a = op[0], b = op[1];   // batches hold < 2^32 bases: the low words
-                noffv = make_uint4(a.x, a.y, b.x, b.y);
-                nst = NST_OFFING;
-            }
-            const uint64_t want_claim = __ballot(nst == NST_CLAIM && phase != P_EXIT);
-            if (want_claim) {
-                const int me = vlane();
-                clead = (uint32_t)(__builtin_ffsll((long long)want_claim) - 1);
-                if (nst == NST_CLAIM && phase != P_EXIT) {
-                    nrank = (int)__popcll(want_claim & ((1ull << me) - 1));
-                    if ((uint32_t)me == clead) {
-                        // the returning atomic by hand: the compiler's form
-                        // (the atomic optimizer's readfirstlane of the result)
-                        // waits for it right here.  The value is read at the top
-                        // of the next iteration, after this iteration's
-                        // s_waitcnt vmcnt(0) below has drained it.
-                        const int cnt = (int)__popcll(want_claim);
-                        asm volatile("global_atomic_add %0, %1, %2, off sc0"
-                                     : "=v"(natom)
-                                     : "v"(P.head), "v"(cnt)
-                                     : "memory");
-                    }
-                    nst = NST_CLAIMING;
-                }
-            }
-        }
-        // prev[j+1] (the owner of a helped batch: prev[j+1+bat_m]) and the query
-        // window land in LDS slots (no VGPR-destination load the compiler would
-        // wait on right away); read back after the wait
-        const uint32_t pidx = (uint32_t)j + 1 + (DU && dq ? 1u : 0u) + (uint32_t)bat_m;
-        const bool ld_pn = phase == P_BWD_RES && pidx < prev_n && !(NL > 0 && prev_lds && pidx < (uint32_t)NL);
-        const bool ld_q = qwant != qb && qwant != ~0u;
-        if (ld_pn)
-            __builtin_amdgcn_global_load_lds(bp + prev_off + pidx, LDS_PTR(&W->pn[0]),
-                                             16, 0, 0);
-        if (ld_q)
-            __builtin_amdgcn_global_load_lds(P.codes + qwant, LDS_PTR(&W->q[0]), 16, 0, 0);
-        // the interval to extend: ik forward (a = x[1]), prev[j] backward (a = x[0]),
-        // a helper's entry backward
-        want = want || helper;
-        const bool fwd = phase == P_FWD_RES;
-        const uint64_t hx0 = p_x0(hent), hx1 = p_x1(hent), hx2 = p_x2(hent);
-        const uint64_t ra = helper ? hx0 : (fwd ? ik1 : ik0), rb = helper ? hx1 : (fwd ? ik0 : ik1),
-                       rs = helper ? hx2 : ik2;
-        const int rc = helper ? hc : cur_c;
-        const uint64_t k = ra - 1, l = k + rs;
-        const uint64_t kk = k - (k >= P.primary), ll = l - (l >= P.primary);
-        Bucket vk, vl;
-        Bucket32 wk, wl;
-        // DU: the second extend (prev[j + 1], same base) and the next pn2
-        const bool want2 = DU && want && !helper && phase == P_BWD_RES && dq;
-        uint64_t ra2 = 0, rb2 = 0, rs2 = 0, kk2 = 0, ll2 = 0;
-        int s_k2 = -1, s_l2 = -1;
-        uint4 v2k0 = {0, 0, 0, 0}, v2k1 = {0, 0, 0, 0}, v2l0 = {0, 0, 0, 0}, v2l1 = {0, 0, 0, 0};
-        const bool ld_pn2 = DU && phase == P_BWD_RES && pidx + 1 < prev_n;
-        const bool pn2_lds = NL > 0 && prev_lds && pidx + 1 < (uint32_t)NL;
-        uint4 pn2_g = {0, 0, 0, 0};
-        if constexpr (DU) {
-            if (ld_pn2 && !pn2_lds) pn2_g = *reinterpret_cast<const uint4*>(bp + prev_off + pidx + 1);
-        }
-        // KT: the result string's length and codes; a short one is one table probe
-        bool ktp = false;
-        uint4 ktv = {0, 0, 0, 0};
-        if constexpr (KT) {
-            const int lq = fwd ? i + 1 - x : (int)ikend - i;
-            ktp = want && !helper && lq <= K;
-            if (ktp) {
-                const uint32_t code = fwd ? kreq : kb >> (2 * (K - lq));
-                const uint64_t base = ((1ull << (2 * lq)) - 4) / 3;
-                ktv = P.kt[base + code];
-            }
-        }
-        if constexpr (VS) {
-            if (want && !ktp)
-                fetch_occ64_issue_regs<L192, (NTM & 1) != 0>(L192 ? P.occ192 : P.occ64, kk, ll, tag0, tag1, fks, fls, s0a,
-                                                             s0b, s1a, s1b);
-            if constexpr (DU) {
-                if (want2) {
-                    ra2 = p_x0(ent2), rb2 = p_x1(ent2), rs2 = p_x2(ent2);
-                    const uint64_t k2 = ra2 - 1, l2 = k2 + rs2;
-                    kk2 = k2 - (k2 >= P.primary), ll2 = l2 - (l2 >= P.primary);
-                    const uint32_t bk2 = (uint32_t)(kk2 >> 6), bl2 = (uint32_t)(ll2 >> 6);
-                    s_k2 = bk2 == tag0 ? 0 : 1;  // both are in the slots (checked above)
-                    s_l2 = bl2 == tag0 ? 0 : 1;
-                }
-            }
-            if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(2);
-            const int ks = fks < 0 ? 0 : fks, ls = fls < 0 ? 0 : fls;
-            wk = ks == 0 ? Bucket32{s0a, s0b} : Bucket32{s1a, s1b};
-            wl = ls == 0 ? Bucket32{s0a, s0b} : Bucket32{s1a, s1b};
-        } else if constexpr (FETCH == FETCH_OCC64) {
-            // lanes whose fetch was not issued early in BWD_RES issue it now
-            if (want && !early)
-                fetch_occ64_issue<WaveLds, L192>(L192 ? P.occ192 : P.occ64, W, kk, ll, tag0, tag1, fks, fls);
-            if constexpr (DU) {
-                if (want2) {
-                    ra2 = p_x0(ent2), rb2 = p_x1(ent2), rs2 = p_x2(ent2);
-                    const uint64_t k2 = ra2 - 1, l2 = k2 + rs2;
-                    kk2 = k2 - (k2 >= P.primary), ll2 = l2 - (l2 >= P.primary);
-                    const uint32_t bk2 = (uint32_t)(kk2 >> 6), bl2 = (uint32_t)(ll2 >> 6);
-                    s_k2 = bk2 == tag0 ? 0 : (bk2 == tag1 ? 1 : -1);
-                    s_l2 = bl2 == tag0 ? 0 : (bl2 == tag1 ? 1 : (bl2 == bk2 ? 2 : -1));
-                    if (s_k2 < 0) {
-                        const uint32_t *c0, *c1;
-                        block_chunks<false>(P.occ64, bk2, c0, c1);
-                        v2k0 = *reinterpret_cast<const uint4*>(c0);
-                        v2k1 = *reinterpret_cast<const uint4*>(c1);
-                    }
-                    if (s_l2 < 0) {
-                        const uint32_t *c0, *c1;
-                        block_chunks<false>(P.occ64, bl2, c0, c1);
-                        v2l0 = *reinterpret_cast<const uint4*>(c0);
-                        v2l1 = *reinterpret_cast<const uint4*>(c1);
-                    }
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            fetch_occ64_read(W, fks, fls, wk, wl);
-        } else {
-            fetch_buckets<FETCH>(P.bwt, W, want, kk, ll, vk, vl);  // ends with vmcnt(0)
-        }
-        if (ld_pn) pn = W->pn[vlane()];
-        if constexpr (NL > 0) {  // prev[pidx] from the LDS list: read here, off the advance's critical path
-            if (phase == P_BWD_RES && prev_lds && pidx < prev_n && pidx < (uint32_t)NL)
-                pn = WLs->e[LSLOT(lr, pidx)][vlane()];
-        }
-        if constexpr (DU) {
-            if (ld_pn2) pn2 = pn2_lds ? WLs->e[LSLOT(lr, pidx + 1)][vlane()] : pn2_g;
-        }
-        if (ld_q) {
-            qv = W->q[vlane()];
-            qb = qwant;
-        }
-        uint64_t tc = 0;
-        if constexpr (STAMP) {
-            tc = stamp();
-            st_fetch += tc - tb;
-        }
-        if constexpr (DU && VS) {
-            if (want2) {
-                const Bucket32 wk2 = s_k2 == 0 ? Bucket32{s0a, s0b} : Bucket32{s1a, s1b};
-                const Bucket32 wl2 = s_l2 == 0 ? Bucket32{s0a, s0b} : Bucket32{s1a, s1b};
-                extend_counts64<false>(P, ra2, rb2, rs2, cur_c, kk2, ll2, wk2, wl2, na2, nb2, ns2);
-            }
-        } else if constexpr (DU) {
-            if (want2) {
-                const int lane2 = vlane();
-                const Bucket32 wk2 = s_k2 >= 0 ? Bucket32{W->img[2 * s_k2][lane2], W->img[2 * s_k2 + 1][lane2]}
-                                               : Bucket32{v2k0, v2k1};
-                const Bucket32 wl2 = s_l2 == 2 ? wk2
-                                     : s_l2 >= 0 ? Bucket32{W->img[2 * s_l2][lane2], W->img[2 * s_l2 + 1][lane2]}
-                                                 : Bucket32{v2l0, v2l1};
-                extend_counts64<false>(P, ra2, rb2, rs2, cur_c, kk2, ll2, wk2, wl2, na2, nb2, ns2);
-            }
-        }
-        if (ktp) {  // forward: na is the x[1] side (ik1), backward: the x[0] side
-            na = fwd ? p_x1(ktv) : p_x0(ktv);
-            nb = fwd ? p_x0(ktv) : p_x1(ktv);
-            ns = p_x2(ktv);
-        } else if (want) {
-            if constexpr (FETCH == FETCH_OCC64)
-                extend_counts64<L192>(P, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
-            else
-                extend_counts(P, ra, rb, rs, rc, kk, ll, vk, vl, na, nb, ns);
-        }
-        if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(0);
-        if (helper) {  // entry + result for the owner's next BWD_RES
-            W->pn[vlane()] = hent;
-            W->q[vlane()] = pack_p(na, nb, ns, 0);
-        }
-        if constexpr (STAMP) {
-            asm volatile("" ::"v"(na), "v"(nb), "v"(ns));
-            st_comp += stamp() - tc;
-        }
-    }
-#undef FWD_PUSH
-#undef LSLOT
-    if (P.tspan && lane == 0) atomicMax(reinterpret_cast<unsigned long long*>(P.tspan) + 1, (unsigned long long)rtstamp());
-    if constexpr (STAMP) {
-        st_t1 = rtstamp();
-        if (lane == 0 && P.dbg_buf) {
-            uint64_t* o = P.dbg_buf + (lane_g >> 6) * 32;
-            o[0] = st_adv; o[1] = st_fetch; o[2] = st_comp; o[3] = st_iter; o[4] = st_active; o[5] = st_t0; o[6] = st_t1;
-            for (int k = 0; k < 16; ++k) o[8 + k] = scnt[threadIdx.x >> 6][k];
-        }
-    }
 }
 
 // ======================================================================
@@ -1328,6 +517,7 @@ struct WpWave {
     uint64_t res1[PAIR ? 64 : 1];  // PAIR: of the lane's first entry
     uint8_t tabS[64];     // owner whose segment starts at task position p (0xFF: none)
     uint8_t tabP[64];     // free-lane rank -> lane
+    uint4 pend[2][OWN];   // each owner's even-indexed raw record, held for the odd one that completes its line
 };
 
 // the OR of v over the 64 lanes (the same pattern; lane 63 holds it)
@@ -1420,7 +610,6 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
     int nitem = 0, nlen = -2;
     uint32_t clead = 0;  // the last claim's leader lane (wave-uniform); its atomic's return lands in no0
     int rid = 0, nrid = 0;
-    uint32_t keep_n = 0;
     uint32_t o0 = 0, no0 = 0;
     uint32_t qb = ~0u, qwant = ~0u;
     uint4 qv = {0, 0, 0, 0};
@@ -1435,7 +624,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
     uint32_t lr = 0;           // forward: the ring position; backward: the slot of list index 0
     uint32_t fail0 = 0;        // entry 0 of the current step failed (its SMEM candidate)
     uint64_t last_x2 = 0;      // size of the last entry kept in curr (dedup across chunks of a step)
-    uint32_t mem_n = 0, mem_last_start = 0, m_n = 0;
+    uint32_t mem_n = 0, mem_last_start = 0;
     uint32_t max_len = 0, max_x2 = 0, max_mid = 0;
     uint4 head = {0, 0, 0, 0};  // prev[0] of the current step
     uint64_t na = 0, nb = 0, ns = 0;
@@ -1445,23 +634,43 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
 #define WSLOT(r_, k_) ((r_) >= (k_) ? (r_) - (k_) : (r_) + (uint32_t)NL - (k_))
 // a SMEM of the current call: the raw log entry, the merge's keep count and
 // the longest match (software/bwt.c:817-819, software/bwamem.c:266-270, 284-292)
+// Only what the merge keeps is logged (every match; a sub-match of at least
+// half the longest match that ends after the call's start), tagged with the
+// call's ordinal and the sub-match bit (smem_kernels.h), so the read's logged
+// count is its final interval count.  Records go out as whole 64-B lines: an
+// even-indexed one waits in LDS for the odd one that follows it.
 #define WP_EMIT(e_)                                                                                          \
     {                                                                                                        \
         const uint4 me_ = (e_);                                                                              \
-        if (raw_n >= P.cap_intv) {                                                                           \
-            phase = P_OVF;                                                                                   \
-        } else {                                                                                             \
-            const uint32_t b_ = (uint32_t)(i + 1), en_ = p_end(me_);                                         \
-            put_rec<false>(P.out_intv + (uint64_t)item * P.cap_intv + raw_n++,                               \
-                           Intv{p_x0(me_), p_x1(me_), p_x2(me_), (uint64_t)en_ | ((uint64_t)b_ << 32)});    \
-            keep_n += !middle || (en_ - b_ >= (max_len >> 1) && en_ > (uint32_t)ori_start);                 \
-            ++mem_n;                                                                                         \
-            mem_last_start = b_;                                                                             \
-            if (!middle && en_ - b_ >= max_len) {                                                            \
-                max_len = en_ - b_;                                                                          \
-                max_x2 = p_x2(me_) > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)p_x2(me_);                      \
-                max_mid = (en_ + b_) >> 1;                                                                   \
+        const uint32_t b_ = (uint32_t)(i + 1), en_ = p_end(me_);                                             \
+        if (!middle || (en_ - b_ >= (max_len >> 1) && en_ > (uint32_t)ori_start)) {                          \
+            if (raw_n >= P.cap_intv) {                                                                       \
+                phase = P_OVF;                                                                               \
+            } else {                                                                                         \
+                const uint64_t x0_ = p_x0(me_), x1_ = p_x1(me_), x2_ = p_x2(me_);                            \
+                const uint32_t tag_ = (uint32_t)(x0_ >> 32) | calls_n << (RAW_ORD_SHIFT - 32) |              \
+                                      (middle ? RAW_SUB_BIT << (RAW_ORD_SHIFT - 32) : 0u);                   \
+                const uint4 lo_ = make_uint4((uint32_t)x0_, tag_, (uint32_t)x1_, (uint32_t)(x1_ >> 32));     \
+                const uint4 hi_ = make_uint4((uint32_t)x2_, (uint32_t)(x2_ >> 32), en_, b_);                 \
+                if (raw_n & 1) {                                                                             \
+                    uint4* ln_ = reinterpret_cast<uint4*>(P.out_intv + (uint64_t)item * P.slot_intv + (raw_n - 1)); \
+                    ln_[0] = L->pend[0][me];                                                                 \
+                    ln_[1] = L->pend[1][me];                                                                 \
+                    ln_[2] = lo_;                                                                            \
+                    ln_[3] = hi_;                                                                            \
+                } else {                                                                                     \
+                    L->pend[0][me] = lo_;                                                                    \
+                    L->pend[1][me] = hi_;                                                                    \
+                }                                                                                            \
+                ++raw_n;                                                                                     \
             }                                                                                                \
+        }                                                                                                    \
+        ++mem_n;                                                                                             \
+        mem_last_start = b_;                                                                                 \
+        if (!middle && en_ - b_ >= max_len) {                                                                \
+            max_len = en_ - b_;                                                                              \
+            max_x2 = p_x2(me_) > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)p_x2(me_);                          \
+            max_mid = (en_ + b_) >> 1;                                                                       \
         }                                                                                                    \
     }
 
@@ -1526,9 +735,8 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             if (phase == P_SMEM_END) {
                 if (!middle) {  // software/bwamem.c:261-272
                     start = ret;
-                    m_n = mem_n;
                     const int split_len = P.split_len_init < len ? P.split_len_init : len;
-                    if (m_n > 0 && split_len > 0 && (int)max_len >= split_len &&
+                    if (mem_n > 0 && split_len > 0 && (int)max_len >= split_len &&
                         (uint64_t)max_x2 <= (uint64_t)(int64_t)P.split_width) {
                         x = (int)max_mid;  // re-seed from the middle (software/bwamem.c:272-278)
                         min_intv = (int)(max_x2 + 1);
@@ -1536,19 +744,12 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                         phase = P_SMEM_BEGIN;
                     }
                 }
-                if (phase == P_SMEM_END) {
-                    if (calls_n >= P.cap_calls) {
-                        phase = P_OVF;
-                    } else {
-                        put_rec<false>(P.out_call + (uint64_t)item * P.cap_calls + calls_n++,
-                                       CallRec{m_n, middle ? mem_n : 0u, (uint32_t)ori_start, max_len});
-                        phase = P_NEXT2;
-                    }
+                if (phase == P_SMEM_END) {  // the call's records carry its ordinal: nothing else to log
+                    ++calls_n;
+                    phase = P_NEXT2;
                 }
             }
-            if (phase == P_OVF) {
-                P.n_intv[item] = SMEM_OVERFLOW;
-                P.n_calls[item] = 0;
+            if (phase == P_OVF) {  // (the record pending in LDS is dropped with the read's log)
                 const int slot = atomicAdd(P.ovf_count, 1);
                 P.ovf_items[slot] = item;
                 phase = P_FETCH;
@@ -1561,7 +762,6 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                 } else {
                     item = nitem;
                     rid = nrid;
-                    keep_n = 0;
                     o0 = no0;
                     len = nlen;
                     nlen = -2;
@@ -1569,10 +769,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                     calls_n = 0;
                     start = 0;
                     if (len < P.min_seed_len) {  // mem_chain's guard (software/bwamem.c:600)
-                        P.n_intv[item] = 0;
-                        P.n_calls[item] = 0;
-                        P.s_intv[rid] = 0;
-                        P.s_calls[rid] = 0;
+                        *reinterpret_cast<uint4*>(P.sizes + 2 * (uint64_t)rid) = make_uint4(0, 0, 0, 0);
                         out = true;
                     } else {
                         phase = P_NEXT2;
@@ -1593,10 +790,12 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                     qwant = QBLK(start);
                     out = true;
                 } else if (start >= len || start < 0) {
-                    P.n_intv[item] = raw_n;
-                    P.n_calls[item] = calls_n;
-                    P.s_intv[rid] = keep_n;
-                    P.s_calls[rid] = calls_n;
+                    if (raw_n & 1) {  // an odd count: the last record goes out alone
+                        uint4* ln_ = reinterpret_cast<uint4*>(P.out_intv + (uint64_t)item * P.slot_intv + (raw_n - 1));
+                        ln_[0] = L->pend[0][me];
+                        ln_[1] = L->pend[1][me];
+                    }
+                    *reinterpret_cast<uint4*>(P.sizes + 2 * (uint64_t)rid) = make_uint4(raw_n, 0, calls_n, 0);
                     phase = P_FETCH;
                 } else {
                     ori_start = start;
@@ -1984,8 +1183,11 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
 
 // Raw logs -> the lists smem_next2 returns: reverse each bwt_smem1 output
 // (software/bwt.c:830) and merge matches with sub-matches keyed by
-// (start, len - end), keeping a sub-match only if it is at least half the
-// longest match and ends after the call's start (software/bwamem.c:280-301).
+// (start, len - end) (software/bwamem.c:280-301).  The log holds only what
+// the merge keeps (the seeding kernel applies :287-288's filter when it
+// emits), so a read's records map one to one onto its output; a call's extent
+// is the run of its ordinal, the match / sub-match split its tag bit
+// (smem_kernels.h).
 // Four threads per read, one per 8-B word of bwtintv_t: all four walk the
 // same merge (on the info words) and each moves its own word, so a wave's
 // loads and stores touch 16 intervals' lines instead of 64.  The per-read
@@ -1994,58 +1196,53 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeParams F) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int r = (int)(t >> 2), w = (int)(t & 3);
     if (r >= F.n) return;
-    const Intv* raw = F.main_intv + (uint64_t)r * F.cap_intv;
-    const CallRec* rec = F.main_call + (uint64_t)r * F.cap_calls;
-    uint32_t nc = F.n_calls[r];
-    if (F.n_intv[r] == SMEM_OVERFLOW) {
-        const int s = F.ovf_slot[r];
-        raw = F.ovf_intv + (uint64_t)s * F.ovf_cap_intv;
-        rec = F.ovf_call + (uint64_t)s * F.ovf_cap_calls;
-        nc = F.ovf_n_calls[s];
-    }
+    const int s = F.ovf_slot ? F.ovf_slot[r] : -1;
+    const Intv* raw = s >= 0 ? F.ovf_intv + (uint64_t)s * F.ovf_slot_intv : F.main_intv + (uint64_t)r * F.slot_intv;
+    const uint32_t nraw = (uint32_t)F.sizes[2 * (uint64_t)r], nc = (uint32_t)F.sizes[2 * (uint64_t)r + 1];
     const uint32_t len = (uint32_t)(F.offs[r + 1] - F.offs[r]);
     const uint64_t* rw = reinterpret_cast<const uint64_t*>(raw);
     uint64_t* ow = reinterpret_cast<uint64_t*>(F.flat_intv + F.intv_off[r]);
     const uint64_t cout = F.call_off[r];
-    uint32_t pos = 0, out = 0;
+    const uint64_t wmask = w == 0 ? RAW_COORD_MASK : ~0ull;  // x0 sheds its tag
+    uint32_t pos = 0;
     for (uint32_t c = 0; c < nc; ++c) {
-        const CallRec cr = rec[c];
+        // the call's records: m_n matches, then s_n sub-matches (none at all: an empty list)
+        uint32_t m_n = 0, s_n = 0;
+        for (uint32_t k = pos; k < nraw; ++k) {
+            const uint32_t tag = (uint32_t)(rw[(uint64_t)k * 4] >> RAW_ORD_SHIFT);
+            if ((tag & RAW_ORD_MASK) != (c & RAW_ORD_MASK)) break;
+            if (tag & RAW_SUB_BIT) ++s_n;
+            else ++m_n;
+        }
         // M[m_n-1-a] is the a-th match in final order; likewise S for sub-matches
         const uint64_t* M = rw + (uint64_t)pos * 4;
-        const uint64_t* S = rw + (uint64_t)(pos + cr.m_n) * 4;
-        const uint64_t half = (uint64_t)(cr.max_len >> 1);
-        uint32_t a = 0, b = 0, n = 0;
-        while (a < cr.m_n || b < cr.s_n) {
+        const uint64_t* S = rw + (uint64_t)(pos + m_n) * 4;
+        uint64_t* o = ow + (uint64_t)pos * 4 + w;
+        uint32_t a = 0, b = 0;
+        while (a < m_n || b < s_n) {
             bool take_m;
-            uint64_t si = 0;
-            if (b >= cr.s_n) {
+            if (b >= s_n) {
                 take_m = true;
+            } else if (a >= m_n) {
+                take_m = false;
             } else {
-                si = S[(uint64_t)(cr.s_n - 1 - b) * 4 + 3];
-                if (a >= cr.m_n) {
-                    take_m = false;
-                } else {
-                    const uint64_t mi = M[(uint64_t)(cr.m_n - 1 - a) * 4 + 3];
-                    const uint64_t xi = (mi >> 32 << 32) | (uint64_t)(uint32_t)(len - (uint32_t)mi);
-                    const uint64_t xj = (si >> 32 << 32) | (uint64_t)(uint32_t)(len - (uint32_t)si);
-                    take_m = (int64_t)xi < (int64_t)xj;
-                }
+                const uint64_t si = S[(uint64_t)(s_n - 1 - b) * 4 + 3];
+                const uint64_t mi = M[(uint64_t)(m_n - 1 - a) * 4 + 3];
+                const uint64_t xi = (mi >> 32 << 32) | (uint64_t)(uint32_t)(len - (uint32_t)mi);
+                const uint64_t xj = (si >> 32 << 32) | (uint64_t)(uint32_t)(len - (uint32_t)si);
+                take_m = (int64_t)xi < (int64_t)xj;
             }
             if (take_m) {
-                ow[(uint64_t)(out + n) * 4 + w] = M[(uint64_t)(cr.m_n - 1 - a) * 4 + w];
-                ++n;
+                *o = M[(uint64_t)(m_n - 1 - a) * 4 + w] & wmask;
                 ++a;
             } else {
-                if ((uint64_t)(uint32_t)si - (si >> 32) >= half && (uint32_t)si > cr.ori_start) {
-                    ow[(uint64_t)(out + n) * 4 + w] = S[(uint64_t)(cr.s_n - 1 - b) * 4 + w];
-                    ++n;
-                }
+                *o = S[(uint64_t)(s_n - 1 - b) * 4 + w] & wmask;
                 ++b;
             }
+            o += 4;
         }
-        if (w == 0) F.flat_calls[cout + c] = n;
-        out += n;
-        pos += cr.m_n + cr.s_n;
+        if (w == 0) F.flat_calls[cout + c] = m_n + s_n;
+        pos += m_n + s_n;
     }
 }
 
@@ -2063,14 +1260,15 @@ __global__ void ovf_slot_kernel(const int32_t* __restrict__ items, int n_ovf, in
 
 // ------------------------------------------------------------ host launchers
 // The product build instantiates the default kernel (seed_wp_kernel variant 49;
-// 0 names it too) and its k-mer table twin (54).  Every other seeding kernel
-// measured in rounds 1-5 (seed_kernel variants 2-31; the seed_wp_kernel shapes
-// and OPT-bit twins 40-62 other than 49 / 54) is compiled only
-// with SMEM_AB_VARIANTS (make AB=1): the library ships no kernel whose numbers
-// are already recorded.
+// 0 names it too) and its k-mer table twin (54).  The other seed_wp_kernel
+// shapes and OPT-bit twins measured in round 5 (40-62 other than 49 / 54;
+// DESIGN.md §5) are compiled only with SMEM_AB_VARIANTS (make AB=1): the
+// library ships no kernel whose numbers are already recorded.  (Rounds 1-4's
+// one-lane-per-read seed_kernel, variants 2-31, wrote the raw log format of
+// its time and left with it; its numbers are in DESIGN.md §5.)
 extern "C" int smem_seed_variant_built(int variant) {
 #ifdef SMEM_AB_VARIANTS
-    return variant == 0 || (variant >= 2 && variant <= 31) || (variant >= 40 && variant <= 62);
+    return variant == 0 || (variant >= 40 && variant <= 62);
 #else
     return variant == 0 || variant == 49 || variant == 54;
 #endif
@@ -2079,25 +1277,6 @@ extern "C" int smem_seed_variant_built(int variant) {
 extern "C" hipError_t smem_launch_seed(const smem::SeedParams* P, int grid, int block, int variant, hipStream_t st) {
     switch (variant) {
 #ifdef SMEM_AB_VARIANTS
-        // 2 (20 and 26 name it too): round 4's default seed_kernel -- Occ64, the two bucket slots per
-        // lane in registers, 11 list entries per lane in LDS (the forward list as a ring of its last 11
-        // pushes), wave priority raised from the top of an iteration until its loads are issued (PRIO 1)
-        case 2: case 20: case 26: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, false, true, false, false, 1>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 9: variant 2 (wave priority included) with cycle stamps
-        case 9: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, true, 3, 11, true, false, false, true, false, true, false, false, 1>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 23: the default with the k-mer table (P->kt)
-        case 23: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, false, true, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 24: the default with the next read claimed and loaded in the uniform section (PFCH); 25: its stamped twin
-        case 24: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, false, true, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 25: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, true, 3, 11, true, false, false, true, false, true, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 27: wave priority raised in the extend arithmetic instead (PRIO 2: no change measured);
-        // 28: the default without wave priority (round-2 default; 2 % slower, profiles/r03/ab/prio)
-        case 28: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 27: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, false, true, false, false, 2>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 29-31: the default with non-temporal bucket loads (29), raw output stores (30), both (31)
-        case 29: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, false, true, false, false, 1, 1>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 30: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, false, true, false, false, 1, 2>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 31: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, false, true, false, false, 1, 3>), dim3(grid), dim3(block), 0, st, *P); break;
         // 40-43: the backward phase wave-parallel over list entries (seed_wp_kernel<owners per wave,
         // LDS list entries per owner, wave priority>)
         case 40: hipLaunchKernelGGL((smem::seed_wp_kernel<32, 20, 1>), dim3(grid), dim3(block), 0, st, *P); break;
@@ -2130,31 +1309,6 @@ extern "C" hipError_t smem_launch_seed(const smem::SeedParams* P, int grid, int 
         case 60: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 11>), dim3(grid), dim3(block), 0, st, *P); break;
         case 61: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 14>), dim3(grid), dim3(block), 0, st, *P); break;
         case 62: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 7>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 3: reference-layout buckets, cooperative fetch, lists in global memory;
-        // 4: reference layout, per-lane fetch; 5: Occ64 with 12 list entries in
-        // LDS at 2 blocks per CU; 6: Occ64, lists in global memory; 7: the
-        // default with the bucket fetch of BWD_RES lanes issued inside the
-        // advance (no gain measured: the fetch is throughput-bound); 8: 4 blocks per CU
-        // with 4 list entries in LDS
-        case 3: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_COOP, false, 3, 0>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 4: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_LANE, false, 3, 0>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 5: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 2, 12>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 6: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 0>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 7: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, smem::LIST_LDS, true, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 8: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 4, 4>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 10: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, smem::LIST_LDS, true, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 11: the first round-2 layout (LDS bucket slots, 7 list entries, forward ring)
-        case 11: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, smem::LIST_LDS, true, false, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 12: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 2, 12, true, false, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 13: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, smem::LIST_LDS>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 14: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 4, 4, true, false, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 15: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 4, 3, true, false, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 16: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, smem::LIST_LDS, true, false, false, true, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 17: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 2, 12, true, false, false, true, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 18: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 2, 13, true, false, false, true, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 19: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, false, true, true, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 21: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 4, 7, true, false, false, true, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        case 22: hipLaunchKernelGGL((smem::seed_kernel<smem::FETCH_OCC64, false, 3, 11, true, false, true, true, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
 #endif
         // 54: the default's shape with the k-mer table (KT; smem_gpu_set_kmer_table, no table: plain)
         case 54: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
@@ -2242,11 +1396,12 @@ __device__ __forceinline__ uint64_t block_excl(uint64_t tsum, uint64_t& total) {
     return before + inc - tsum;
 }
 
-__global__ __launch_bounds__(SCAN_T) void scan_tile_sums(const uint64_t* __restrict__ in, int n, uint64_t* __restrict__ bsum) {
+__global__ __launch_bounds__(SCAN_T) void scan_tile_sums(const uint64_t* __restrict__ in, int stride, int n,
+                                                         uint64_t* __restrict__ bsum) {
     const int64_t b0 = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_I;
     uint64_t t = 0;
 #pragma unroll
-    for (int k = 0; k < SCAN_I; ++k) t += b0 + k < n ? in[b0 + k] : 0;
+    for (int k = 0; k < SCAN_I; ++k) t += b0 + k < n ? in[(b0 + k) * stride] : 0;
     uint64_t total;
     (void)block_excl(t, total);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
@@ -2274,13 +1429,14 @@ __global__ __launch_bounds__(SCAN_T) void scan_tile_offsets(uint64_t* __restrict
     }
 }
 
-__global__ __launch_bounds__(SCAN_T) void scan_tiles(const uint64_t* __restrict__ in, int n,
-                                                     const uint64_t* __restrict__ boff, uint64_t* __restrict__ out) {
+__global__ __launch_bounds__(SCAN_T) void scan_tiles(const uint64_t* __restrict__ in, int stride, int n,
+                                                     const uint64_t* __restrict__ boff, uint64_t* __restrict__ out,
+                                                     uint64_t* __restrict__ total_out) {
     const int64_t b0 = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_I;
     uint64_t v[SCAN_I], t = 0;
 #pragma unroll
     for (int k = 0; k < SCAN_I; ++k) {
-        v[k] = b0 + k < n ? in[b0 + k] : 0;
+        v[k] = b0 + k < n ? in[(b0 + k) * stride] : 0;
         t += v[k];
     }
     uint64_t total;
@@ -2290,26 +1446,37 @@ __global__ __launch_bounds__(SCAN_T) void scan_tiles(const uint64_t* __restrict_
     for (int k = 0; k < SCAN_I; ++k) {
         run += v[k];
         if (b0 + k < n) out[b0 + k + 1] = run;
+        if (total_out && b0 + k == n - 1) *total_out = run;
     }
 }
 }  // namespace smem
 
-// out[0] = 0, out[1..n] = inclusive sums of in[0..n-1]; temp == nullptr
-// queries the temporary size into *temp_bytes
-extern "C" hipError_t smem_launch_offsets(const uint64_t* in, uint64_t* out, int n, void* temp, size_t* temp_bytes,
-                                          hipStream_t st) {
+// out[0] = 0, out[1..n] = inclusive sums of in[0], in[stride], .. in[(n-1) stride];
+// temp == nullptr queries the temporary size into *temp_bytes; total != nullptr
+// receives out[n] too (a word the caller copies back with its other scalars)
+extern "C" hipError_t smem_launch_offsets_strided(const uint64_t* in, int stride, uint64_t* out, int n, void* temp,
+                                                  size_t* temp_bytes, uint64_t* total, hipStream_t st) {
     const int nb = n > 0 ? (n + smem::SCAN_TILE - 1) / smem::SCAN_TILE : 1;
     if (temp == nullptr) {
         *temp_bytes = sizeof(uint64_t) * (size_t)(nb + 1);
         return hipSuccess;
     }
     if (*temp_bytes < sizeof(uint64_t) * (size_t)nb) return hipErrorInvalidValue;
-    if (n <= 0) return hipMemsetAsync(out, 0, sizeof(uint64_t), st);
+    if (n <= 0) {
+        hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t), st);
+        if (e == hipSuccess && total) e = hipMemsetAsync(total, 0, sizeof(uint64_t), st);
+        return e;
+    }
     uint64_t* bsum = static_cast<uint64_t*>(temp);
-    hipLaunchKernelGGL(smem::scan_tile_sums, dim3(nb), dim3(smem::SCAN_T), 0, st, in, n, bsum);
+    hipLaunchKernelGGL(smem::scan_tile_sums, dim3(nb), dim3(smem::SCAN_T), 0, st, in, stride, n, bsum);
     hipLaunchKernelGGL(smem::scan_tile_offsets, dim3(1), dim3(smem::SCAN_T), 0, st, bsum, nb);
-    hipLaunchKernelGGL(smem::scan_tiles, dim3(nb), dim3(smem::SCAN_T), 0, st, in, n, bsum, out);
+    hipLaunchKernelGGL(smem::scan_tiles, dim3(nb), dim3(smem::SCAN_T), 0, st, in, stride, n, bsum, out, total);
     return hipGetLastError();
+}
+
+extern "C" hipError_t smem_launch_offsets(const uint64_t* in, uint64_t* out, int n, void* temp, size_t* temp_bytes,
+                                          hipStream_t st) {
+    return smem_launch_offsets_strided(in, 1, out, n, temp, temp_bytes, nullptr, st);
 }
 
 namespace smem {
