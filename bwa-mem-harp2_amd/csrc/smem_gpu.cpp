@@ -37,6 +37,7 @@
 #include "chain_kernels.h"
 #include "ksw_kernels.h"
 #include "aln_kernels.h"
+#include "global_kernels.h"
 
 using smem::Intv;
 
@@ -2618,6 +2619,182 @@ int smem_chain2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint6
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     if (kernel_ms) *kernel_ms = ms;
+    return SMEM_OK;
+}
+
+// ---- regions -> alignments (mem_reg2aln's alignment part, software/bwamem.c:1504-1547)
+static_assert(sizeof(smem_aln_t) == sizeof(smem::Aln), "alignment layout");
+static_assert(SMEM_ALN_UNMAPPED == smem::G2A_UNMAPPED && SMEM_ALN_NOCIGAR == smem::G2A_NOCIGAR &&
+              SMEM_ALN_REJECT == smem::G2A_REJECT, "alignment status values");
+
+int smem_reg2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_t* offs, const smem_alnreg_t* regs,
+                 const uint64_t* reg_off, const uint8_t* pac, int64_t l_pac, const smem_aln_opt_t* opt,
+                 smem_aln_t* alns, uint32_t* cigar, uint64_t cigar_cap, uint64_t* n_cigar_words, char* md,
+                 uint64_t md_cap, uint64_t* n_md_bytes, double* kernel_ms) {
+    g_err[0] = 0;
+    if (!g || n_reads < 0 || !opt || !n_cigar_words || !n_md_bytes ||
+        (n_reads > 0 && (!codes || !offs || !reg_off)) || l_pac <= 0 || (cigar_cap > 0 && !cigar) ||
+        (md_cap > 0 && !md))
+        return fail(SMEM_E_ARG, "smem_reg2aln: bad arguments");
+    if (!pac && !(g->d_pac && g->l_pac == l_pac))
+        return fail(SMEM_E_ARG, "smem_reg2aln: no pac given and none resident for this l_pac (smem_gpu_load_pac)");
+    if (!aln_opt_ok(opt)) return fail(SMEM_E_ARG, "smem_reg2aln: scoring needs e >= 1, o >= 0, a >= 1, w >= 0");
+    if (kernel_ms) *kernel_ms = 0.0;
+    *n_cigar_words = *n_md_bytes = 0;
+    if (n_reads == 0) return SMEM_OK;
+    for (int r = 0; r < n_reads; ++r)
+        if (offs[r + 1] < offs[r] || offs[r + 1] - offs[r] > (1u << 30) || reg_off[r + 1] < reg_off[r])
+            return fail(SMEM_E_ARG, "smem_reg2aln: offsets not ascending");
+    const uint64_t n_bases = offs[n_reads], n_regs = reg_off[n_reads];
+    if (n_regs >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_reg2aln: too many regions");
+    if (n_regs > 0 && (!regs || !alns)) return fail(SMEM_E_ARG, "smem_reg2aln: no region / alignment buffer");
+    // query codes index the 25-entry scoring matrix: 0..4 only
+    for (uint64_t k = offs[0]; k < n_bases; ++k)
+        if (codes[k] > 4) return fail(SMEM_E_ARG, "smem_reg2aln: query code > 4");
+    // every region is settled here (unmapped, no CIGAR, outside the limits) or becomes a
+    // task whose shape the host has checked; tasks go to the lane-group size their first
+    // band asks for, or straight to the scratch-tier launch when no group's LDS holds them
+    const smem_ksw_opt_t& sc = opt->sc;
+    std::vector<smem::G2aTask> tasks;
+    std::vector<uint32_t> list[4];  // 16, 32, 64 lanes; scratch tier
+    tasks.reserve(n_regs);
+    for (int r = 0; r < n_reads; ++r) {
+        const int64_t l_query = (int64_t)(offs[r + 1] - offs[r]);
+        for (uint64_t k = reg_off[r]; k < reg_off[r + 1]; ++k) {
+            const smem_alnreg_t& R = regs[k];
+            smem_aln_t& A = alns[k];
+            std::memset(&A, 0, sizeof(A));
+            A.pos = -1;
+            if (R.rb < 0 || R.re < 0) {  // software/bwamem.c:1489
+                A.status = SMEM_ALN_UNMAPPED;
+                continue;
+            }
+            if (R.qb < 0 || R.qe > l_query) return fail(SMEM_E_ARG, "smem_reg2aln: region outside its read");
+            // bwa_gen_cigar2 returns 0 (software/bwa.c:106-108)
+            if (R.qe <= R.qb || R.rb >= R.re || (R.rb < l_pac && R.re > l_pac) || R.re > 2 * l_pac) {
+                A.status = SMEM_ALN_NOCIGAR, A.NM = -1, A.tries = 1;
+                continue;
+            }
+            if (R.qe - R.qb > smem::G2A_MAX_QLEN || R.re - R.rb > smem::G2A_MAX_TLEN) {
+                A.status = SMEM_ALN_REJECT;
+                continue;
+            }
+            smem::G2aTask T;
+            T.q_off = offs[r] + (uint64_t)R.qb, T.rb = R.rb, T.re = R.re, T.qlen = R.qe - R.qb, T.qb = R.qb;
+            T.l_query = (int32_t)l_query, T.truesc = R.truesc, T.w = R.w, T.out = (uint32_t)k;
+            const int tlen = (int)(R.re - R.rb);
+            const int w2 = smem::g2a_first_w2(T.qlen, tlen, R.truesc, opt->a, sc.o_del, sc.e_del, sc.o_ins, sc.e_ins,
+                                              opt->w, R.w);
+            int n_col = 1;
+            uint64_t need = (uint64_t)smem::g2a_fixed_bytes(T.qlen, tlen);
+            if (!(T.qlen == tlen && w2 == 0)) {
+                const int w = smem::g2a_band(T.qlen, tlen, sc.mat[0], sc.o_del, sc.e_del, sc.o_ins, sc.e_ins, w2);
+                n_col = std::min(T.qlen, 2 * w + 1);
+                need += (uint64_t)smem::g2a_row_bytes(T.qlen, w) * tlen;
+            }
+            int cls = n_col <= 16 ? 0 : n_col <= 32 ? 1 : 2;
+            while (cls < 3 && need > (uint64_t)smem::g2a_group_lds(16 << cls)) ++cls;
+            list[cls].push_back((uint32_t)tasks.size());
+            tasks.push_back(T);
+        }
+    }
+    const uint64_t n_tasks = tasks.size();
+    if (n_tasks == 0) return SMEM_OK;
+    DevBuf<uint8_t> dcodes, dpac, dscratch;
+    DevBuf<smem::G2aTask> dtask;
+    DevBuf<uint32_t> dlist, dcig;
+    DevBuf<smem::Aln> daln;
+    DevBuf<char> dmd;
+    DevBuf<unsigned long long> dcur;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct Guard {
+        std::function<void()> f;
+        ~Guard() { f(); }
+    } guard{[&] {
+        dcodes.release(); dpac.release(); dscratch.release(); dtask.release(); dlist.release(); dcig.release();
+        daln.release(); dmd.release(); dcur.release();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }};
+    DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
+    if (call.rc) return call.rc;
+    const hipStream_t st = call.st;
+    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
+    const uint64_t pac_bytes = (uint64_t)(l_pac + 3) / 4;
+    HIP_TRY(dcodes.ensure(n_bases + 64));
+    if (pac) HIP_TRY(dpac.ensure(pac_bytes + 64));
+    HIP_TRY(dtask.ensure(n_tasks));
+    HIP_TRY(dlist.ensure(2 * n_tasks));  // the three group lists, then room for the deferred ones
+    HIP_TRY(daln.ensure(n_regs));
+    HIP_TRY(dcig.ensure(cigar_cap));
+    HIP_TRY(dmd.ensure(md_cap));
+    HIP_TRY(dcur.ensure(4));
+    if (n_bases) HIP_TRY(hipMemcpyAsync(dcodes.p, codes, n_bases, hipMemcpyHostToDevice, st));
+    if (pac) HIP_TRY(hipMemcpyAsync(dpac.p, pac, pac_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dtask.p, tasks.data(), sizeof(smem::G2aTask) * n_tasks, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dcur.p, 0, 4 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(daln.p, 0, sizeof(smem::Aln) * n_regs, st));
+    smem::G2aParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.task = dtask.p, P.codes = dcodes.p, P.pac = pac ? dpac.p : g->d_pac, P.l_pac = l_pac;
+    std::memcpy(P.mat, sc.mat, 25);
+    P.o_del = sc.o_del, P.e_del = sc.e_del, P.o_ins = sc.o_ins, P.e_ins = sc.e_ins, P.a = opt->a, P.w = opt->w;
+    P.alns = daln.p, P.cigar = dcig.p, P.md = dmd.p, P.cigar_cap = cigar_cap, P.md_cap = md_cap, P.cur = dcur.p;
+    uint64_t at = 0;
+    HIP_TRY(hipEventRecord(ev[0], st));
+    for (int c = 0; c < 3; ++c) {
+        if (list[c].empty()) continue;
+        HIP_TRY(hipMemcpyAsync(dlist.p + at, list[c].data(), 4 * list[c].size(), hipMemcpyHostToDevice, st));
+        P.list = dlist.p + at, P.n = (uint32_t)list[c].size();
+        HIP_TRY(smem_launch_g2a(&P, 16 << c, st));
+        at += list[c].size();
+    }
+    HIP_TRY(hipEventRecord(ev[1], st));
+    unsigned long long cur[4] = {0, 0, 0, 0};
+    std::vector<smem::Aln> got(n_regs);
+    HIP_TRY(hipMemcpyAsync(cur, dcur.p, sizeof(cur), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(got.data(), daln.p, sizeof(smem::Aln) * n_regs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f, ms2 = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    // a retry's wider band outgrew its group's LDS: those regions again, with the scratch tier
+    if (cur[2])
+        for (uint64_t k = 0; k < n_tasks; ++k)
+            if (got[tasks[k].out].status == smem::G2A_DEFERRED) list[3].push_back((uint32_t)k);
+    if (!list[3].empty()) {
+        uint64_t stride = 0;
+        for (uint32_t k : list[3]) {
+            const smem::G2aTask& T = tasks[k];
+            const int tlen = (int)(T.re - T.rb);
+            const int w = smem::g2a_band(T.qlen, tlen, sc.mat[0], sc.o_del, sc.e_del, sc.o_ins, sc.e_ins, INT32_MAX);
+            stride = std::max<uint64_t>(stride, (uint64_t)smem::g2a_row_bytes(T.qlen, w) * tlen);
+        }
+        stride = std::max<uint64_t>((stride + 255) & ~255ull, 256);
+        uint64_t blocks = std::max<uint64_t>(smem::G2A_BIG_BLOCKS_MIN, smem::G2A_BIG_SCRATCH / stride);
+        blocks = std::min<uint64_t>(std::min<uint64_t>(blocks, smem::G2A_BIG_BLOCKS_MAX), list[3].size());
+        HIP_TRY(dscratch.ensure(blocks * stride + 256));
+        HIP_TRY(hipMemcpyAsync(dlist.p + at, list[3].data(), 4 * list[3].size(), hipMemcpyHostToDevice, st));
+        P.list = dlist.p + at, P.n = (uint32_t)list[3].size();
+        P.scratch = dscratch.p, P.scratch_stride = stride;
+        HIP_TRY(hipEventRecord(ev[2], st));
+        HIP_TRY(smem_launch_g2a_big(&P, (uint32_t)blocks, st));
+        HIP_TRY(hipEventRecord(ev[3], st));
+        HIP_TRY(hipMemcpyAsync(cur, dcur.p, sizeof(cur), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(got.data(), daln.p, sizeof(smem::Aln) * n_regs, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipEventElapsedTime(&ms2, ev[2], ev[3]));
+    }
+    if (kernel_ms) *kernel_ms = (double)ms + (double)ms2;
+    for (uint64_t k = 0; k < n_tasks; ++k) {
+        const smem::Aln& A = got[tasks[k].out];
+        if (A.status != smem::G2A_OK) return fail(SMEM_E_INTERNAL, "smem_reg2aln: a region's traceback left its band");
+        std::memcpy(&alns[tasks[k].out], &A, sizeof(A));
+    }
+    *n_cigar_words = cur[0], *n_md_bytes = cur[1];
+    if (cur[0] > cigar_cap || cur[1] > md_cap) return fail(SMEM_E_CAPACITY, "smem_reg2aln: cigar / md pool too small");
+    if (cur[0]) HIP_TRY(hipMemcpyAsync(cigar, dcig.p, 4 * cur[0], hipMemcpyDeviceToHost, st));
+    if (cur[1]) HIP_TRY(hipMemcpyAsync(md, dmd.p, cur[1], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return SMEM_OK;
 }
 

@@ -37,6 +37,7 @@ EXPORTED = [
     "smem_gpu_reserve_slots", "smem_gpu_set_max_active", "smem_gpu_get_max_active", "smem_gpu_kernel_id", "smem_gpu_fault",
     "smem_batch_memory", "smem_gpu_memory", "smem_gpu_init_devices_async", "smem_gpu_wait_ready",
     "smem_gpu_open_async", "smem_gpu_load_sa_async", "smem_gpu_load_pac_async",
+    "smem_reg2aln",
 ]
 
 # smem_batch_fetch_mask bits (include/smem_gpu.h)
@@ -144,6 +145,16 @@ def aln_opt(**kw) -> AlnOptT:
 
 SEED_DT = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4")])          # smem_seed_t = mem_seed_t
 CHAIN_DT = np.dtype([("pos", "<i8"), ("seed_off", "<u8"), ("n", "<i4"), ("pad", "<i4")])  # smem_chain_t
+# smem_alnreg_t = mem_alnreg_t (the 64-byte records chain2aln returns)
+ALNREG_DT = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"), ("truesc", "<i4"),
+                      ("sub", "<i4"), ("csub", "<i4"), ("sub_n", "<i4"), ("w", "<i4"), ("seedcov", "<i4"),
+                      ("secondary", "<i4"), ("hash", "<u8")])
+# smem_aln_t
+ALN_DT = np.dtype([("pos", "<i8"), ("is_rev", "<i4"), ("n_cigar", "<i4"), ("NM", "<i4"), ("score", "<i4"),
+                   ("tries", "<i4"), ("status", "<i4"), ("cigar_off", "<u8"), ("md_off", "<u8"), ("md_len", "<i4"),
+                   ("pad", "<i4")])
+ALN_UNMAPPED, ALN_NOCIGAR, ALN_REJECT = 1, 2, 3
+SMEM_E_CAPACITY = -6
 
 
 _lib = None
@@ -184,6 +195,9 @@ def load() -> C.CDLL:
     lib.smem_chain2aln.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                    P(C.c_double)]
+    lib.smem_reg2aln.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_uint64),
+                                 C.c_void_p, C.c_uint64, P(C.c_uint64), P(C.c_double)]
     lib.smem_chain_opt_default.argtypes = [P(ChainOptT)]
     lib.smem_chain_opt_default.restype = None
     lib.smem_batch_chain.argtypes = [C.c_void_p, C.c_int64, P(ChainOptT)]
@@ -651,6 +665,50 @@ class Gpu:
                                   pac.ctypes.data if pac is not None else None, l_pac,
                                   C.byref(opt), regs.ctypes.data, reg_off.ctypes.data, C.byref(ms)), "smem_chain2aln")
         return regs[:int(reg_off[-1]) * 64], reg_off, ms.value
+
+    def reg2aln(self, pac, l_pac: int, codes, offs, regs, reg_off, opt, cigar_cap: int | None = None,
+                md_cap: int | None = None) -> tuple:
+        """The alignment part of mem_reg2aln (software/bwamem.c:1504-1547) of
+        every region on this device (smem_reg2aln): regs are smem_alnreg_t
+        records (ALNREG_DT, or the raw bytes chain2aln returns), reg_off the
+        regions of each read, pac None for the resident .pac.  Returns (alns
+        as ALN_DT, cigar words, md bytes, kernel ms); region k's CIGAR is
+        cigar[cigar_off : cigar_off + n_cigar] and its MD md[md_off : md_off +
+        md_len].  The pools start at cigar_cap words / md_cap bytes (default:
+        a guess from the regions) and the call is repeated with the sizes the
+        library reports when they are too small."""
+        lib = load()
+        if pac is not None:
+            pac = np.ascontiguousarray(pac, dtype=np.uint8)
+            if pac.size < (int(l_pac) + 3) // 4:
+                raise SmemError("reg2aln: pac holds fewer than (l_pac + 3) / 4 bytes")
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.uint64)
+        regs = np.ascontiguousarray(regs)
+        if regs.dtype != ALNREG_DT:
+            regs = np.frombuffer(regs.astype(np.uint8, copy=False).tobytes(), dtype=ALNREG_DT)
+        if reg_off.size != offs.size or (reg_off.size and int(reg_off[-1]) > regs.size):
+            raise SmemError("reg2aln: reg_off must have n_reads + 1 entries within regs")
+        n = offs.size - 1
+        n_regs = int(reg_off[-1]) if reg_off.size else 0
+        alns = np.zeros(max(n_regs, 1), dtype=ALN_DT)
+        cap_c = 8 * n_regs if cigar_cap is None else int(cigar_cap)
+        cap_m = 24 * n_regs if md_cap is None else int(md_cap)
+        ms = C.c_double()
+        while True:
+            cigar = np.zeros(max(cap_c, 1), dtype=np.uint32)
+            md = np.zeros(max(cap_m, 1), dtype=np.uint8)
+            nc, nm = C.c_uint64(), C.c_uint64()
+            rc = lib.smem_reg2aln(self._h, n, codes.ctypes.data, offs.ctypes.data, regs.ctypes.data,
+                                  reg_off.ctypes.data, pac.ctypes.data if pac is not None else None, l_pac,
+                                  C.byref(opt), alns.ctypes.data, cigar.ctypes.data, cap_c, C.byref(nc),
+                                  md.ctypes.data, cap_m, C.byref(nm), C.byref(ms))
+            if rc == SMEM_E_CAPACITY and (nc.value > cap_c or nm.value > cap_m):
+                cap_c, cap_m = max(cap_c, int(nc.value)), max(cap_m, int(nm.value))
+                continue
+            _check(rc, "smem_reg2aln")
+            return alns[:n_regs], cigar[:int(nc.value)], md[:int(nm.value)], ms.value
 
     def close(self) -> None:
         if self._h:

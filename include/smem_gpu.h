@@ -482,6 +482,49 @@ int  smem_batch_chain2aln(smem_batch_t *b, const smem_aln_opt_t *opt);
 int  smem_batch_aln_results(const smem_batch_t *b, const smem_alnreg_t **regs, const uint64_t **reg_off,
                             uint64_t *n_regs);
 
+/* ------------------------------------------- regions -> alignments */
+#define SMEM_ALN_UNMAPPED 1
+#define SMEM_ALN_NOCIGAR  2
+#define SMEM_ALN_REJECT   3
+/* what mem_reg2aln (software/bwamem.c:1481-1553) makes of one region, short of
+ * the contig lookup, MAPQ and flags */
+typedef struct {
+	int64_t  pos;        /* 0-based forward-strand coordinate in the concatenated .pac (bns_depos of
+	                        rb, or of re-1 on the reverse strand), after a leading deletion was squeezed out;
+	                        -1 when status != 0 */
+	int32_t  is_rev, n_cigar, NM, score;   /* score: ksw_global2's of the last try */
+	int32_t  tries;      /* 1..3 bwa_gen_cigar2 calls made (the band-doubling loop) */
+	int32_t  status;     /* 0 ok; SMEM_ALN_UNMAPPED (rb<0 or re<0); SMEM_ALN_NOCIGAR (bwa_gen_cigar2
+	                        returned 0: empty, or bridging l_pac; NM -1, tries 1); SMEM_ALN_REJECT (outside
+	                        the limits below: the caller does it on the CPU, the reference's reject -> CPU
+	                        convention) */
+	uint64_t cigar_off;  /* into cigar[]: n_cigar words, len<<4|op, op 0 M 1 I 2 D 3 S (clips as mem_reg2aln adds them) */
+	uint64_t md_off; int32_t md_len, pad;  /* into md[]: the MD string, no terminator */
+} smem_aln_t;
+/* The alignment part of mem_reg2aln for every region of every read, on the GPU:
+ * the band from infer_bw (software/bwamem.c:1194-1201, 1504-1508), up to three
+ * bwa_gen_cigar2 calls with a doubled band (software/bwamem.c:1511-1518;
+ * software/bwa.c:96-179: banded global alignment with traceback, ksw_global2,
+ * software/ksw.c:501-584, then NM and MD), the squeeze of a leading or trailing
+ * deletion and the clips (software/bwamem.c:1523-1547).  Host buffers in and out,
+ * the resident .pac when pac == NULL.  regs[reg_off[r] .. reg_off[r+1]) are the
+ * regions of read r in doubled coordinates, as smem_chain2aln returns them; rb,
+ * re, qb, qe, truesc and w are read.  One smem_aln_t per region, in region
+ * order; cigar_off / md_off need not ascend.  bwa_fix_xref2 (software/bwamem.c:1500)
+ * needs the contig table and stays with the caller: every region must already
+ * lie within one contig, and pos is in concatenated coordinates (contig id and
+ * offset are the caller's).  Limits: qe - qb <= 1024 and re - rb <= 2048;
+ * a region outside them gets SMEM_ALN_REJECT and the call goes on.
+ * SMEM_E_CAPACITY when cigar_cap words or md_cap bytes do not hold the output:
+ * *n_cigar_words / *n_md_bytes then give the sizes a retry needs (on success,
+ * the sizes used).  SMEM_E_ARG for query codes above 4, a region outside its
+ * read and a missing resident .pac. */
+int  smem_reg2aln(smem_gpu_t *gpu, int n_reads, const uint8_t *codes, const uint64_t *offs,
+                  const smem_alnreg_t *regs, const uint64_t *reg_off,
+                  const uint8_t *pac, int64_t l_pac, const smem_aln_opt_t *opt,
+                  smem_aln_t *alns, uint32_t *cigar, uint64_t cigar_cap, uint64_t *n_cigar_words,
+                  char *md, uint64_t md_cap, uint64_t *n_md_bytes, double *kernel_ms);
+
 /* ---------------------------------------------------------- telemetry */
 typedef struct {
 	double kernel_ms;        /* seeding kernel(s), HIP events on the batch stream */
