@@ -323,6 +323,17 @@ void orc_seed_uses(uint64_t out[4], int reset)
 	if (reset) memset(orc_seed_use, 0, sizeof(orc_seed_use));
 }
 
+/* extensions of at most 256 query columns whose scores can pass 16 bits
+ * (h0 + qlen * top > 65535), per thread: what a 16-bit DP has to refuse */
+__thread uint64_t orc_ext_wide;
+
+uint64_t orc_ext_wide16(int reset)
+{
+	const uint64_t n = orc_ext_wide;
+	if (reset) orc_ext_wide = 0;
+	return n;
+}
+
 static int extend(const orc_aln_opt_t *o, int qlen, const uint8_t *q, int tlen, const uint8_t *t, int w,
 		int end_bonus, int h0, orc_ksw_result_t *res)
 {
@@ -330,6 +341,9 @@ static int extend(const orc_aln_opt_t *o, int qlen, const uint8_t *q, int tlen, 
 	uint64_t c0 = orc_cells_ext;
 	orc_ksw_task_t T;
 	orc_ksw_opt_t ko;
+	int shift, top;
+	orc_sw_shift_top(o->mat, &shift, &top);
+	if (qlen >= 1 && qlen <= 256 && (int64_t)(h0 > 0 ? h0 : 0) + (int64_t)qlen * top > 65535) orc_ext_wide += 1;
 	memset(&T, 0, sizeof(T));
 	T.qlen = qlen, T.tlen = tlen, T.w = w, T.end_bonus = end_bonus, T.zdrop = o->zdrop, T.h0 = h0;
 	memcpy(ko.mat, o->mat, 25);

@@ -108,6 +108,8 @@ def load() -> C.CDLL:
         lib.orc_ext_shapes.restype = None
         lib.orc_seed_uses.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         lib.orc_seed_uses.restype = None
+        lib.orc_ext_wide16.argtypes = [C.c_int]
+        lib.orc_ext_wide16.restype = C.c_uint64
         lib.orc_ksw_align2.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.POINTER(C.c_int32)]
         lib.orc_ksw_align2.restype = None
@@ -463,6 +465,13 @@ def seed_uses(reset: bool = True) -> dict:
     load().orc_seed_uses(out, 1 if reset else 0)
     return dict(first_extended=int(out[0]), other_extended=int(out[1]), first_skipped=int(out[2]),
                 seeds=int(out[3]))
+
+
+def ext_wide16(reset: bool = True) -> int:
+    """How many of the restatement's chain2aln extensions on this thread had at
+    most 256 query columns and h0 + qlen * (largest score) > 65535: the
+    extensions a 16-bit DP cannot hold."""
+    return int(load().orc_ext_wide16(1 if reset else 0))
 
 
 def aln(pac, l_pac: int, codes, offs, chains, chain_off, seeds, opt: AlnOptT):

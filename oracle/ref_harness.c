@@ -30,17 +30,20 @@
  *       written as SMCH (include/smem_formats.h).
  *   aln   <in.bwt> <in.sa> <in.pac> <reads.smrd> <out.smrg> <k> <r> <s> <start_width> <max_occ> <w>
  *         <max_chain_gap> <mask_level> <drop_ratio>
+ *         [<a> <b> <o_del> <e_del> <o_ins> <e_ins> <zdrop> <pen_clip5> <pen_clip3>]
  *       mem_chain + mem_chain_flt as for chain (filter on), then per chain
  *       mem_chain2aln_short and, when it declines, mem_chain2aln
  *       (software/bwamem.c:1452-1460); every read's regions written as SMRG (and the
  *       wall time of the chain2aln loop alone on stderr: "chain2aln_seconds=..."):
  *       "SMRG0001", u64 n_reads, per read u32 n then n x {i64 rb, re;
  *       i32 qb, qe, score, truesc, sub, csub, sub_n, w, seedcov, secondary}.
+ *       The nine optional scoring fields of mem_opt_t are taken literally (no
+ *       -A scaling) and bwa_fill_scmat is called after them.
  *   kswa  <tasks.smat> <out.smar>
  *       the reference's own ksw_align2 (software/ksw.c:342) on every task
  *       (SMAT: as SMKT with per task {u64 q_off, t_off; i32 qlen, tlen, xtra, pad}),
  *       results as SMAR: "SMAR0001", u64 n, n x i32 {score, te, qe, score2, te2, tb, qb}.
- *   mem   <prefix> <reads.fq> <n_threads> <batch_size> <pe> [<pg>]
+ *   mem   <prefix> <reads.fq> <n_threads> <batch_size> <pe> [<pg> [-k|-w|-A|-B|-O|-E|-L|-d <value>]...]
  *       The body of the reference's main_mem (software/fastmap.c:193-230) on the
  *       unmodified pipeline: bwa_print_sam_hdr, then bseq_read chunks through
  *       mem_process_seqs (software/bwamem.c:1614: kt_for_batch -> worker1_batched
@@ -52,6 +55,8 @@
  *       :324) are allocated the same way.  With batch_size <= 2 every batch takes
  *       bwt_smem1_batched's CPU path (software/bwt.c:603, 686-717): this is
  *       `bwa mem -t N -b 1` of the reference, the golden SAM for the GPU build.
+ *       The options after <pg> are read as main_mem reads them
+ *       (software/fastmap.c:54-94), -A scaling what was not given (:159-171).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -346,7 +351,12 @@ static int cmd_aln(int argc, char **argv)
 	double t_aln = 0.0;
 	uint64_t n_regs = 0;
 	if (argc < 15) {
-		fprintf(stderr, "usage: aln <bwt> <sa> <pac> <reads> <out> <k> <r> <s> <sw> <max_occ> <w> <gap> <mask> <drop>\n");
+		fprintf(stderr, "usage: aln <bwt> <sa> <pac> <reads> <out> <k> <r> <s> <sw> <max_occ> <w> <gap> <mask> <drop>"
+				" [a b o_del e_del o_ins e_ins zdrop pen_clip5 pen_clip3]\n");
+		return 1;
+	}
+	if (argc != 15 && argc != 24) {
+		fprintf(stderr, "aln: the scoring arguments come all nine or not at all\n");
 		return 1;
 	}
 	opt = mem_opt_init();
@@ -359,6 +369,14 @@ static int cmd_aln(int argc, char **argv)
 	opt->max_chain_gap = atoi(argv[12]);
 	opt->mask_level = (float)atof(argv[13]);
 	opt->chain_drop_ratio = (float)atof(argv[14]);
+	if (argc == 24) {  /* literal values: no -A scaling of the others (software/fastmap.c:111-120) */
+		opt->a = atoi(argv[15]); opt->b = atoi(argv[16]);
+		opt->o_del = atoi(argv[17]); opt->e_del = atoi(argv[18]);
+		opt->o_ins = atoi(argv[19]); opt->e_ins = atoi(argv[20]);
+		opt->zdrop = atoi(argv[21]);
+		opt->pen_clip5 = atoi(argv[22]); opt->pen_clip3 = atoi(argv[23]);
+		bwa_fill_scmat(opt->a, opt->b, opt->mat);
+	}
 	bwt = bwt_restore_bwt(argv[1]);
 	bwt_restore_sa(argv[2], bwt);
 	l_pac = (int64_t)(bwt->seq_len >> 1);
@@ -494,6 +512,49 @@ extern unsigned long int **worker_mem;
 extern volatile unsigned char *sw_handshake;
 extern char *bwa_pg;
 
+/* `bwa mem`'s scoring options as main_mem reads them (software/fastmap.c:54-94,
+ * 159-171): -k -w -A -B -O -E -L -d, INT or INT,INT where bwa takes a pair; -A
+ * scales the penalties, T, zdrop and the clip penalties that were not given */
+static int pair_arg(const char *s, int *x, int *y)
+{
+	char *p;
+	*x = *y = (int)strtol(s, &p, 10);
+	if (*p == ',' && p[1] >= '0' && p[1] <= '9') *y = (int)strtol(p + 1, &p, 10);
+	return *p == 0 ? 0 : -1;
+}
+
+static int mem_options(mem_opt_t *opt, int n, char **av)
+{
+	int i, set_a = 0, set_b = 0, set_o = 0, set_e = 0, set_l = 0, set_d = 0;
+	if (n & 1) return -1;
+	for (i = 0; i < n; i += 2) {
+		const char *k = av[i], *v = av[i + 1];
+		if (k[0] != '-' || k[1] == 0 || k[2] != 0) return -1;
+		switch (k[1]) {
+		case 'k': opt->min_seed_len = atoi(v); break;
+		case 'w': opt->w = atoi(v); break;
+		case 'A': opt->a = atoi(v); set_a = 1; break;
+		case 'B': opt->b = atoi(v); set_b = 1; break;
+		case 'd': opt->zdrop = atoi(v); set_d = 1; break;
+		case 'O': if (pair_arg(v, &opt->o_del, &opt->o_ins)) return -1; set_o = 1; break;
+		case 'E': if (pair_arg(v, &opt->e_del, &opt->e_ins)) return -1; set_e = 1; break;
+		case 'L': if (pair_arg(v, &opt->pen_clip5, &opt->pen_clip3)) return -1; set_l = 1; break;
+		default: return -1;
+		}
+	}
+	if (set_a) {
+		if (!set_b) opt->b *= opt->a;
+		opt->T *= opt->a;
+		if (!set_o) opt->o_del *= opt->a, opt->o_ins *= opt->a;
+		if (!set_e) opt->e_del *= opt->a, opt->e_ins *= opt->a;
+		if (!set_d) opt->zdrop *= opt->a;
+		if (!set_l) opt->pen_clip5 *= opt->a, opt->pen_clip3 *= opt->a;
+		opt->pen_unpaired *= opt->a;
+	}
+	bwa_fill_scmat(opt->a, opt->b, opt->mat);
+	return 0;
+}
+
 static int cmd_mem(int argc, char **argv)
 {
 	mem_opt_t *opt;
@@ -506,12 +567,19 @@ static int cmd_mem(int argc, char **argv)
 	bseq1_t *seqs;
 	int i, n;
 	int64_t n_processed = 0;
-	if (argc < 6) { fprintf(stderr, "usage: mem <prefix> <reads.fq> <threads> <batch> <pe> [pg]\n"); return 1; }
+	if (argc < 6) {
+		fprintf(stderr, "usage: mem <prefix> <reads.fq> <threads> <batch> <pe> [pg [-k|-w|-A|-B|-O|-E|-L|-d VALUE]...]\n");
+		return 1;
+	}
 	opt = mem_opt_init();
 	opt->n_threads = atoi(argv[3]);
 	opt->batch_size = atoi(argv[4]) > 1? atoi(argv[4]) : 1;
 	if (atoi(argv[5])) opt->flag |= MEM_F_PE;
 	bwa_pg = argc > 6? argv[6] : "@PG\tID:bwa\tPN:bwa\tVN:0.7.8-r455";
+	if (argc > 7 && mem_options(opt, argc - 7, argv + 7) != 0) {
+		fprintf(stderr, "mem: bad option list\n");
+		return 1;
+	}
 	tmp = calloc(strlen(argv[1]) + 5, 1);
 	strcat(strcpy(tmp, argv[1]), ".bwt");
 	bwt = bwt_restore_bwt(tmp);

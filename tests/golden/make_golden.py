@@ -31,6 +31,12 @@ reference code itself:
     python tests/golden/make_golden.py --ksw-only      # (re)make only the ksw set
     python tests/golden/make_golden.py --ksw-gap0-only # (re)make only ksw_gap0
     python tests/golden/make_golden.py --kswa-only     # (re)make only the ksw_align2 sets
+    python tests/golden/make_golden.py --aln-only      # (re)make the region fixtures (*.smrg.gz, r3 / r4 and theirs)
+    python tests/golden/make_golden.py --aln-options-only  # (re)make only r3 / r4 and their fixtures
+  r3.smrd.gz, r4.smrd.gz  reads of g1 / g2 with indels, junk stretches, mismatched ends and unrelated
+                      tails (tests/aln_reads.py), their filtered chains <g>_<r>_<std|k10|w1|w7>_std_f1.smch.gz
+  <g>_<r>_<set>.smrg.gz  the reference's regions of those reads under each option set of
+                      aln_reads.OPTION_SETS (`ref_harness aln` with the scoring arguments)
   kswa_a<1|2>.smat.gz 3000 ksw_align2 problems shaped like mem_chain2aln_short's (a = 1, 2)
   kswa_a<1|2>.smar.gz the reference's own ksw_align2 on each (software/ksw.c:342)
   kswa_<set>.sma[tr].gz  up to 600 each (KSWA_MORE): o_ins = 0 at a = 1 and 2, asymmetric gaps,
@@ -538,11 +544,93 @@ def make_aln():
             json.dump(manifest, fh, indent=1)
     finally:
         shutil.rmtree(tmp)
+    make_aln_options()
+
+
+# chains -> regions under non-default extension options (bwa mem -d / -L / -B /
+# -O / -E / -A / -w / -k): read sets r3 (g1) and r4 (g2) of tests/aln_reads.py,
+# their filtered chains, and the reference's regions under every option set of
+# aln_reads.OPTION_SETS.  mem_chain reads opt->w and opt->min_seed_len too, so
+# the w1 / w7 / k10 sets have chains of their own.
+# genome, read set, seed, reads beside the 28 long ones
+OPT_READS = [("g1", "r3", 301, 520), ("g2", "r4", 302, 255)]
+# k10: the first 230 reads (seeds of 10 bp make several times the chains and regions)
+OPT_CHAINS = [dict(name="std", min_seed_len=19, w=100), dict(name="k10", min_seed_len=10, w=100, n_reads=230),
+              dict(name="w1", min_seed_len=19, w=1), dict(name="w7", min_seed_len=19, w=7)]
+OPT_CHAIN_OF = {"k10": "k10", "w1": "w1", "w7": "w7"}   # option set -> chain set (the others: std)
+
+
+def make_aln_options():
+    from tests import aln_reads, golden_data
+    if not oracle.ref_available():
+        oracle.build(ref=True)
+    tmp = tempfile.mkdtemp()
+    try:
+        with open(os.path.join(HERE, "manifest.json")) as fh:
+            manifest = json.load(fh)
+        std = next(c for c in CHAIN_OPTS if c["name"] == "std")
+        sets, regs = {}, [f for f in manifest.get("aln", []) if "reads" not in f]
+        for g, rname, seed, n in OPT_READS:
+            with gzip.open(os.path.join(HERE, g + ".fa.gz"), "rb") as fh:
+                fa_bytes = fh.read()
+            with open(os.path.join(tmp, g + ".fa"), "wb") as o:
+                o.write(fa_bytes)
+            oracle.ref_index(os.path.join(tmp, g + ".fa"), os.path.join(tmp, g))
+            reads = aln_reads.option_reads(golden_data.fasta_codes(fa_bytes), n, seed)
+            smrd = os.path.join(tmp, rname + ".smrd")
+            synth.write_smrd(smrd, reads)
+            with open(smrd, "rb") as fh:
+                data = fh.read()
+            gz_write(os.path.join(HERE, rname + ".smrd.gz"), data)
+            entry = dict(genome=g, file=rname + ".smrd.gz", n_reads=reads.n, seed=seed,
+                         sha256=hashlib.sha256(data).hexdigest(), chains=[])
+            subs = {}
+            for co in OPT_CHAINS:
+                nr = co.get("n_reads", reads.n)
+                subs[co["name"]] = os.path.join(tmp, f"{rname}_{nr}.smrd")
+                synth.write_smrd(subs[co["name"]], reads.subset(np.arange(nr)))
+                case = dict(opt=dict(min_seed_len=co["min_seed_len"], split_factor=1.5, split_width=10, start_width=1))
+                cd = ref_chain(tmp, subs[co["name"]], case, dict(std, w=co["w"]), 1, genome=g)
+                fn = f"{g}_{rname}_{co['name']}_std_f1.smch.gz"
+                gz_write(os.path.join(HERE, fn), cd)
+                entry["chains"].append(dict(std, name=co["name"], w=co["w"], min_seed_len=co["min_seed_len"], file=fn,
+                                            filter=1, n_reads=nr, sha256=hashlib.sha256(cd).hexdigest()))
+            sets[rname] = entry
+            for oname in aln_reads.OPTION_SETS:
+                o = aln_reads.full_options(oname)
+                chain = next(c for c in entry["chains"] if c["name"] == OPT_CHAIN_OF.get(oname, "std"))
+                assert chain["w"] == o["w"] and chain["min_seed_len"] == o["min_seed_len"]
+                out = os.path.join(tmp, "a.smrg")
+                p = subprocess.run([oracle.REF, "aln", os.path.join(tmp, g + ".bwt"), os.path.join(tmp, g + ".sa"),
+                                    os.path.join(tmp, g + ".pac"), subs[chain["name"]], out, str(o["min_seed_len"]), "1.5", "10", "1",
+                                    str(MAX_OCC), str(o["w"]), str(std["max_chain_gap"]), str(std["mask_level"]),
+                                    str(std["drop_ratio"])] +
+                                   [str(o[k]) for k in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "zdrop",
+                                                        "pen_clip5", "pen_clip3")])
+                if p.returncode != 0:   # the reference itself faults on this set: left out, and said
+                    print(f"ref_harness aln failed on {rname} {oname}: exit {p.returncode}", flush=True)
+                    continue
+                with open(out, "rb") as fh:
+                    data = fh.read()
+                fn = f"{g}_{rname}_{oname}.smrg.gz"
+                gz_write(os.path.join(HERE, fn), data)
+                regs.append(dict(genome=g, case=chain["name"], chain_file=chain["file"], file=fn, w=o["w"],
+                                 min_seed_len=o["min_seed_len"], sha256=hashlib.sha256(data).hexdigest(),
+                                 reads=rname, n_reads=chain["n_reads"], name=oname, opt=o,
+                                 chain_sha256=chain["sha256"]))
+        manifest["aln_reads"] = sets
+        manifest["aln"] = regs
+        with open(os.path.join(HERE, "manifest.json"), "w") as fh:
+            json.dump(manifest, fh, indent=1)
+    finally:
+        shutil.rmtree(tmp)
 
 
 if __name__ == "__main__":
     if "--aln-only" in sys.argv:
         make_aln()
+    elif "--aln-options-only" in sys.argv:
+        make_aln_options()
     elif "--ksw-only" in sys.argv:
         make_ksw()
         make_aln()

@@ -14,6 +14,12 @@ For g1 (300 kbp) and g2 (150 kbp, repeat-dense) of the committed fixtures:
                      mem: main_mem's body over mem_process_seqs, every batch on
                      bwt_smem1_batched's CPU path), index by the reference's own
                      `bwa index -a is`; the @PG line is the harness's.
+  sam/g2_se_<tag>.sam.gz
+                     the same over g2_se.fq.gz under the scoring options of OPTION_RUNS
+                     (`bwa mem -L 0,9 -d 20`, `-A 2 -B 3 -O 5,8 -E 3,2`, `-w 7 -k 14`;
+                     ref_harness mem reads them as main_mem does, -A scaling included)
+
+    python tests/golden/make_golden_sam.py --options-only   # only the OPTION_RUNS files
 """
 import gzip
 import hashlib
@@ -36,6 +42,37 @@ from smemgpu import synth  # noqa: E402
 REF = os.path.join(ROOT, "oracle", "_ref", "ref_harness")
 OUT = os.path.join(HERE, "sam")
 QUAL = 40
+
+
+# tag -> `bwa mem` options (tests/test_bwa_integration.py runs the patched bwa with the same)
+OPTION_RUNS = [("L0_9_d20", ["-L", "0,9", "-d", "20"]),
+               ("A2_B3_O5_8_E3_2", ["-A", "2", "-B", "3", "-O", "5,8", "-E", "3,2"]),
+               ("w7_k14", ["-w", "7", "-k", "14"])]
+PG = "@PG\tID:bwa\tPN:bwa\tVN:0.7.8-r455"
+
+
+def make_options():
+    """g2_se under each option string of OPTION_RUNS; the other files stay as they are"""
+    with open(os.path.join(OUT, "manifest.json")) as fh:
+        man = json.load(fh)
+    with tempfile.TemporaryDirectory() as d:
+        fa = os.path.join(d, "g2.fa")
+        with gzip.open(os.path.join(HERE, "g2.fa.gz"), "rb") as src, open(fa, "wb") as dst:
+            shutil.copyfileobj(src, dst)
+        subprocess.run([REF, "index", fa, fa], check=True, capture_output=True)
+        fq = os.path.join(OUT, "g2_se.fq.gz")
+        for tag, args in OPTION_RUNS:
+            p = subprocess.run([REF, "mem", fa, fq, "1", "1", "0", PG] + args, check=True, capture_output=True)
+            with open(os.path.join(OUT, f"g2_se_{tag}.sam.gz"), "wb") as raw, \
+                    gzip.GzipFile(fileobj=raw, mode="wb", compresslevel=9, mtime=0, filename="") as fh:
+                fh.write(p.stdout)
+            body = b"".join(l + b"\n" for l in p.stdout.split(b"\n") if l and not l.startswith(b"@PG"))
+            man[f"g2_se_{tag}"] = {"reads": man["g2_se"]["reads"], "options": " ".join(args),
+                                   "sam_lines": body.count(b"\n"),
+                                   "sha256_sam_without_pg": hashlib.sha256(body).hexdigest()}
+            print(tag, man[f"g2_se_{tag}"], flush=True)
+    with open(os.path.join(OUT, "manifest.json"), "w") as fh:
+        json.dump(man, fh, indent=1)
 
 
 def write_fastq(path: str, reads, names) -> None:
@@ -86,7 +123,11 @@ def main():
                 print(g, kind, man[f"{g}_{kind}"], flush=True)
     with open(os.path.join(OUT, "manifest.json"), "w") as fh:
         json.dump(man, fh, indent=1)
+    make_options()
 
 
 if __name__ == "__main__":
-    main()
+    if "--options-only" in sys.argv:
+        make_options()
+    else:
+        main()

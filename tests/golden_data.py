@@ -151,6 +151,36 @@ def aln_fixtures():
         return json.load(fh).get("aln", [])
 
 
+def aln_reads(fix):
+    """the reads of a region fixture: the first n_reads of the genome's r1 / r2,
+    or of the read set the fixture names (r3 / r4: tests/aln_reads.py), as
+    smemgpu.synth.Reads"""
+    import tempfile
+    from smemgpu import synth
+    with open(os.path.join(GOLDEN, "manifest.json")) as fh:
+        m = json.load(fh)
+    if "reads" in fix:
+        rs = m["aln_reads"][fix["reads"]]
+        data, n = _gz(rs["file"]), fix["n_reads"]
+        assert hashlib.sha256(data).hexdigest() == rs["sha256"], "fixture corrupted"
+    else:
+        data = _gz("r1.smrd.gz" if fix["genome"] == "g1" else "r2.smrd.gz")
+        n = next(c for c in genome_cases(fix["genome"]) if c["name"] == fix["case"])["n_reads"]
+    with tempfile.TemporaryDirectory() as d:
+        p = os.path.join(d, "r.smrd")
+        with open(p, "wb") as fh:
+            fh.write(data)
+        return synth.read_smrd(p).subset(np.arange(n))
+
+
+def aln_chains(fix) -> bytes:
+    """the filtered chains (SMCH) a region fixture was made over"""
+    if "reads" in fix:
+        return smch(dict(file=fix["chain_file"], sha256=fix["chain_sha256"]))
+    case = next(c for c in genome_cases(fix["genome"]) if c["name"] == fix["case"])
+    return smch(next(c for c in case["chains"] if c["file"] == fix["chain_file"]))
+
+
 def pac(genome: str) -> np.ndarray:
     """the 2-bit forward strand bwa_index wrote (software/bntseq.c:303-309)"""
     n = (l_pac(genome) + 3) // 4

@@ -8,6 +8,9 @@ Golden: tests/golden/sam/*.sam.gz, the unpatched reference pipeline's SAM
 SAM apart from the @PG line -- north_star: "the `bwa mem` CLI and downstream
 chaining/SAM path are unchanged".
 
+* Options: `-L 0,9 -d 20`, `-A 2 -B 3 -O 5,8 -E 3,2` and `-w 7 -k 14` on g2_se,
+  on the CPU path and through the GPU stages, against the reference's SAM
+  under the same options (tests/golden/sam/g2_se_<tag>.sam.gz).
 * CPU (always): without a usable device the patched mem_align1_core_batched
   takes the reject -> CPU path (mem_chain); SAM must still be identical.
 * GPU (-m gpu): the seeding loop, bwt_sa, mem_chain + mem_chain_flt and
@@ -118,9 +121,9 @@ def _golden(g, kind) -> list:
         return [l for l in fh.read().split("\n") if l and not l.startswith("@PG")]
 
 
-def _run(fa, g, kind, threads, batch, env=None):
-    """batch None: no -b (the binding's batch plan)."""
-    args = [BWA, "mem", "-t", str(threads)] + ([] if batch is None else ["-b", str(batch)]) + \
+def _run(fa, g, kind, threads, batch, env=None, extra=()):
+    """batch None: no -b (the binding's batch plan); extra: more `bwa mem` options."""
+    args = [BWA, "mem", "-t", str(threads)] + ([] if batch is None else ["-b", str(batch)]) + list(extra) + \
            (["-p"] if kind == "pe" else []) + [fa, os.path.join(GOLD, "sam", f"{g}_{kind}.fq.gz")]
     # SMEM_GPU_CRASH_TRACE: a host crash prints its backtrace (the library's handler); the whole
     # stderr of a failed run is kept under gpurun_out/ (merged back from a GPU box)
@@ -129,7 +132,9 @@ def _run(fa, g, kind, threads, batch, env=None):
     if p.returncode != 0:
         d = os.path.join(ROOT, "gpurun_out", "bwa_fail")
         os.makedirs(d, exist_ok=True)
-        tag = f"{g}_{kind}_t{threads}_b{batch}_" + "_".join(f"{k}={v}" for k, v in (env or {}).items()).replace(",", ".")
+        tag = f"{g}_{kind}_t{threads}_b{batch}_" + "".join(extra) + "_" + \
+            "_".join(f"{k}={v}" for k, v in (env or {}).items())
+        tag = tag.replace(",", ".")
         with open(os.path.join(d, tag[:120] + ".err"), "w") as fh:
             fh.write(" ".join(args) + "\n" + p.stderr)
     crash = p.stderr.find("[smem crash]")
@@ -144,6 +149,21 @@ def test_cpu_fallback_sam_identical(indexed, g, kind):
     got, err = _run(indexed[g], g, kind, 3, 64, env={"SMEM_GPU_DEVICES": "63"})
     assert "seeding on the CPU" in err
     assert got == _golden(g, kind)
+
+
+# scoring options (tests/golden/make_golden_sam.py OPTION_RUNS: the golden SAM of g2_se under each)
+OPTION_RUNS = [("L0_9_d20", ["-L", "0,9", "-d", "20"]),
+               ("A2_B3_O5_8_E3_2", ["-A", "2", "-B", "3", "-O", "5,8", "-E", "3,2"]),
+               ("w7_k14", ["-w", "7", "-k", "14"])]
+
+
+@pytest.mark.parametrize("tag,extra", OPTION_RUNS, ids=[t for t, _ in OPTION_RUNS])
+def test_cpu_fallback_sam_identical_options(indexed, tag, extra):
+    """`bwa mem -L / -d / -A / -B / -O / -E / -w / -k` with no device: the
+    patched build's CPU path prints the reference's SAM under the same options."""
+    got, err = _run(indexed["g2"], "g2", "se", 3, 64, env={"SMEM_GPU_DEVICES": "63"}, extra=extra)
+    assert "seeding on the CPU" in err
+    assert got == _golden("g2", "se_" + tag)
 
 
 def _same(got, want):
@@ -179,6 +199,18 @@ def test_gpu_sam_identical(indexed, gpu_device, g, kind, threads, batch, mode):
     if mode == "two_ctx":
         assert "2 GPU context(s)" in err, err[-2000:]
     _same(got, _golden(g, kind))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag,extra", OPTION_RUNS, ids=[t for t, _ in OPTION_RUNS])
+def test_gpu_sam_identical_options(indexed, gpu_device, tag, extra):
+    """The scoring, z-drop, clip, band and seed-length options reach the GPU
+    stages (bwamem.c.patch copies them into smem_aln_opt_t; -A scales the rest
+    as main_mem does): seeding -> regions on the MI355X, `-t 3 -b 37`, SAM
+    byte-identical to the reference's under the same options."""
+    got, err = _run(indexed["g2"], "g2", "se", 3, 37, env=GPU_MODES["regions"], extra=extra)
+    assert "seeding on the CPU" not in err and "refused" not in err, err[-2000:]
+    _same(got, _golden("g2", "se_" + tag))
 
 
 @pytest.mark.gpu
