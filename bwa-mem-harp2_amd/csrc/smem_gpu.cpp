@@ -38,6 +38,7 @@
 #include "ksw_kernels.h"
 #include "aln_kernels.h"
 #include "global_kernels.h"
+#include "fin_kernels.h"
 
 using smem::Intv;
 
@@ -94,13 +95,14 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
 // SMEM_E_DEVICE after its work is enqueued and before it is waited for, so
 // the drain on the way out is what keeps that work from landing after the
 // caller resumed.  stage: upload (smem_batch_set_reads*), seed
-// (smem_batch_run), sa, chain, aln (smem_batch_chain2aln), fetch, or any.
+// (smem_batch_run), sa, chain, aln (smem_batch_chain2aln), fin (smem_reg_finalize,
+// smem_batch_reg_finalize), fetch, or any.
 // ":sticky" also marks the device faulted, as a real runtime failure does;
 // ":hip=<code>" goes through fail() with that hipError_t, so the
 // classification decides (hip=9, hipErrorInvalidConfiguration: that call only;
 // hip=719, hipErrorLaunchFailure: the device).
-enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_N };
-const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch"};
+enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_N };
+const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin"};
 std::atomic<uint64_t> g_stage_calls[ST_N];
 
 int inject_fault(int stage) {
@@ -308,6 +310,12 @@ struct smem_gpu {
     int kt_k = 0;
     uint64_t* d_sa = nullptr;       // sampled SA (smem_gpu_load_sa), n_sa + 1 words
     uint8_t* d_pac = nullptr;       // 2-bit forward strand (smem_gpu_load_pac)
+    // raw regions -> final regions: the host libm's log tables (fin_tables), made on first use;
+    // fin_used: a batch has run the stage, so worker slots reserved later carry its buffers
+    double* d_fin_log = nullptr;
+    int32_t* d_fin_subn = nullptr;
+    std::mutex fin_mu;
+    std::atomic<bool> fin_used{false};
     int64_t l_pac = 0;
     uint64_t n_sa = 0;
     uint32_t sa_shift = 0;
@@ -411,6 +419,25 @@ struct AlnHeavyBufs {
     }
 };
 
+// device buffers of raw regions -> final regions (csrc/fin_kernels.h FinParams)
+struct FinBufs {
+    DevBuf<uint32_t> ctr, lane_list, wave_list, tmp_idx;
+    DevBuf<uint64_t> n_out, n_sel, out_off, sel_off, out_idx;
+    DevBuf<int32_t> status;
+    DevBuf<smem::AlnReg> tmp_regs, out_regs;
+    DevBuf<smem::FinSel> tmp_sel, out_sel;
+    DevBuf<uint8_t> scan_tmp;
+    DevBuf<int64_t> ids;
+    template <class F>
+    void each(F&& f) {
+        f(ctr); f(lane_list); f(wave_list); f(tmp_idx); f(n_out); f(n_sel); f(out_off); f(sel_off); f(out_idx);
+        f(status); f(tmp_regs); f(out_regs); f(tmp_sel); f(out_sel); f(scan_tmp); f(ids);
+    }
+    void release() {
+        each([](auto& x) { x.release(); });
+    }
+};
+
 struct smem_batch {
     smem_gpu_t* g = nullptr;
     char* arena_dev = nullptr;   // the blocks a reserved slot's buffers are carved from (Arena)
@@ -492,6 +519,15 @@ struct smem_batch {
     HostBuf<smem::AlnReg> h_aln_regs;
     bool aln_ran = false, aln_fetched = false;
     uint64_t tot_regs = 0;
+    // final regions (smem_batch_reg_finalize): nothing here is allocated until the stage is called
+    FinBufs fin;
+    HostBuf<int64_t> h_fin_ids;
+    HostBuf<uint64_t> h_fin_off, h_fin_idx;   // h_fin_off: out_off[n + 1], then sel_off[n + 1]
+    HostBuf<smem::AlnReg> h_fin_regs;
+    HostBuf<smem::FinSel> h_fin_sel;
+    HostBuf<int32_t> h_fin_status;
+    bool fin_ran = false, fin_fetched = false;
+    uint64_t tot_fin = 0, tot_fin_sel = 0;
     smem_batch_stats_t stats{};
 };
 
@@ -511,6 +547,8 @@ static void batch_bufs(smem_batch_t* b, D&& d, H&& h) {
     h(b->h_chain_off); h(b->h_out_chain); h(b->h_out_seed);
     d(b->d_aln_srt); d(b->d_aln_nregs); d(b->d_aln_regoff); d(b->d_aln_raw);
     d(b->d_aln_out); d(b->d_aln_ctr); b->aln_heavy.each(d); h(b->h_aln_regoff); h(b->h_aln_regs);
+    b->fin.each(d); h(b->h_fin_ids); h(b->h_fin_off); h(b->h_fin_idx); h(b->h_fin_regs); h(b->h_fin_sel);
+    h(b->h_fin_status);
     h(b->h_ctr); h(b->h_tot); h(b->h_intv); h(b->h_calls);
     d(b->d_pintv); h(b->h_pintv); h(b->h_intv_off); h(b->h_call_off);
 }
@@ -934,6 +972,8 @@ void smem_gpu_shutdown(smem_gpu_t* g) {
     if (g->d_sa) (void)hipFree(g->d_sa);
     if (g->d_sa_raw) (void)hipFree(g->d_sa_raw);
     if (g->d_pac) (void)hipFree(g->d_pac);
+    if (g->d_fin_log) (void)hipFree(g->d_fin_log);
+    if (g->d_fin_subn) (void)hipFree(g->d_fin_subn);
     for (auto& p : g->pairs) {
         (void)hipStreamDestroy(p.first);
         (void)hipStreamDestroy(p.second);
@@ -1100,6 +1140,7 @@ static int batch_run_impl(smem_batch_t* b, const smem_opt_t* opt) {
     b->chain_ran = b->chain_fetched = false;
     b->tot_chains = b->tot_seeds = 0;
     b->aln_ran = b->aln_fetched = false;
+    b->fin_ran = b->fin_fetched = false;
     b->tot_regs = 0;
     b->stats = smem_batch_stats_t{};
     b->stats.block = 256;
@@ -1237,10 +1278,11 @@ static int fetch_impl(smem_batch_t* b, int mask) {
     BatchCall call(b);
     if (call.rc) return call.rc;
     // views of an earlier fetch end here (its buffers may be regrown below)
-    b->fetched = b->sa_fetched = b->chain_fetched = b->aln_fetched = false;
+    b->fetched = b->sa_fetched = b->chain_fetched = b->aln_fetched = b->fin_fetched = false;
     const int n = b->n_reads;
     const bool f_intv = mask & SMEM_FETCH_INTV, f_sa = (mask & SMEM_FETCH_SA) && b->sa_ran;
     const bool f_chain = (mask & SMEM_FETCH_CHAINS) && b->chain_ran, f_aln = (mask & SMEM_FETCH_REGS) && b->aln_ran;
+    const bool f_fin = (mask & SMEM_FETCH_FIN) && b->fin_ran;
     // pinned result buffers grow with headroom: a streamed batch whose next
     // chunk holds a few more intervals must not re-pin a gigabyte
     if (!f_intv) {
@@ -1298,8 +1340,33 @@ static int fetch_impl(smem_batch_t* b, int mask) {
             HIP_TRY(hipMemcpyAsync(b->h_aln_regs.p, b->d_aln_out.p, sizeof(smem::AlnReg) * b->tot_regs,
                                    hipMemcpyDeviceToHost, b->st));
     }
+    if (f_fin) {
+        HIP_TRY(b->h_fin_off.grow(2 * ((uint64_t)n + 1)));
+        HIP_TRY(b->h_fin_status.grow((uint64_t)std::max(n, 1)));
+        HIP_TRY(b->h_fin_regs.grow(b->tot_fin));
+        HIP_TRY(b->h_fin_sel.grow(b->tot_fin));
+        HIP_TRY(b->h_fin_idx.grow(b->tot_fin_sel));
+        if (n > 0) {
+            HIP_TRY(hipMemcpyAsync(b->h_fin_off.p, b->fin.out_off.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, b->st));
+            HIP_TRY(hipMemcpyAsync(b->h_fin_off.p + (n + 1), b->fin.sel_off.p, sizeof(uint64_t) * (n + 1),
+                                   hipMemcpyDeviceToHost, b->st));
+            HIP_TRY(hipMemcpyAsync(b->h_fin_status.p, b->fin.status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, b->st));
+        } else {
+            b->h_fin_off.p[0] = b->h_fin_off.p[1] = 0;
+        }
+        if (b->tot_fin) {
+            HIP_TRY(hipMemcpyAsync(b->h_fin_regs.p, b->fin.out_regs.p, sizeof(smem::AlnReg) * b->tot_fin,
+                                   hipMemcpyDeviceToHost, b->st));
+            HIP_TRY(hipMemcpyAsync(b->h_fin_sel.p, b->fin.out_sel.p, sizeof(smem::FinSel) * b->tot_fin,
+                                   hipMemcpyDeviceToHost, b->st));
+        }
+        if (b->tot_fin_sel)
+            HIP_TRY(hipMemcpyAsync(b->h_fin_idx.p, b->fin.out_idx.p, sizeof(uint64_t) * b->tot_fin_sel,
+                                   hipMemcpyDeviceToHost, b->st));
+    }
     INJECT(ST_FETCH);
     HIP_TRY(hipStreamSynchronize(b->st));
+    b->fin_fetched = f_fin;
     b->fetched = f_intv;
     b->sa_fetched = f_sa;
     b->chain_fetched = f_chain;
@@ -1316,9 +1383,9 @@ int smem_batch_fetch(smem_batch_t* b) {
 int smem_batch_fetch_mask(smem_batch_t* b, int mask) {
     g_err[0] = 0;
     if (!b || !b->ran) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: batch has not run");
-    if (mask & ~SMEM_FETCH_ALL) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: unknown bits");
+    if (mask & ~(SMEM_FETCH_ALL | SMEM_FETCH_FIN)) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: unknown bits");
     if (((mask & SMEM_FETCH_SA) && !b->sa_ran) || ((mask & SMEM_FETCH_CHAINS) && !b->chain_ran) ||
-        ((mask & SMEM_FETCH_REGS) && !b->aln_ran))
+        ((mask & SMEM_FETCH_REGS) && !b->aln_ran) || ((mask & SMEM_FETCH_FIN) && !b->fin_ran))
         return fail(SMEM_E_ARG, "smem_batch_fetch_mask: a requested stage has not run on this batch");
     return fetch_impl(b, mask);
 }
@@ -1492,6 +1559,7 @@ int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
     if (call.rc) return call.rc;
     b->sa_ran = b->chain_ran = b->aln_ran = false;
     b->sa_fetched = b->chain_fetched = b->aln_fetched = false;
+    b->fin_ran = b->fin_fetched = false;
     // the densified SA may still be in the making (smem_gpu_load_sa runs it
     // in the background): until its event has passed, the walk goes to the
     // stored samples instead (the same positions, sa_intv / D times the LF
@@ -1558,6 +1626,7 @@ int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
     b->sa_min_seed_len = min_seed_len;
     b->chain_ran = b->chain_fetched = false;
     b->aln_ran = b->aln_fetched = false;
+    b->fin_ran = b->fin_fetched = false;
     return SMEM_OK;
 }
 
@@ -1579,6 +1648,7 @@ int smem_batch_chain(smem_batch_t* b, int64_t l_pac, const smem_chain_opt_t* opt
     if (call.rc) return call.rc;
     b->chain_ran = b->aln_ran = false;
     b->chain_fetched = b->aln_fetched = false;
+    b->fin_ran = b->fin_fetched = false;
     const int n = b->n_reads;
     const uint64_t no = std::max<uint64_t>(b->tot_occ, 1);
     HIP_TRY(b->d_seed.grow(no));
@@ -1686,6 +1756,7 @@ int smem_batch_chain(smem_batch_t* b, int64_t l_pac, const smem_chain_opt_t* opt
     b->chain_fetched = false;
     b->chain_filtered = opt->filter != 0;
     b->aln_ran = b->aln_fetched = false;
+    b->fin_ran = b->fin_fetched = false;
     return SMEM_OK;
 }
 
@@ -2383,6 +2454,7 @@ int smem_batch_chain2aln(smem_batch_t* b, const smem_aln_opt_t* opt) {
     BatchCall call(b, aln_two_streams());
     if (call.rc) return call.rc;
     b->aln_ran = b->aln_fetched = false;
+    b->fin_ran = b->fin_fetched = false;
     const int n = b->n_reads;
     const uint64_t ns = std::max<uint64_t>(b->tot_seeds, 1);
     HIP_TRY(b->d_aln_srt.grow(ns + 1));
@@ -2798,6 +2870,258 @@ int smem_reg2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_
     return SMEM_OK;
 }
 
+// ---- raw regions -> final regions (mem_sort_and_dedup, mem_mark_primary_se, selection, MAPQ
+// and flags: csrc/fin_kernels.hip)
+static_assert(sizeof(smem_fin_sel_t) == sizeof(smem::FinSel), "selection layout");
+static_assert(SMEM_FIN_MAX_REGS == smem::FIN_MAX_REGS && SMEM_FIN_TAB_LEN == smem::FIN_TAB_LEN &&
+              SMEM_FIN_REJECT == smem::FIN_REJECT, "finalize limits");
+
+void smem_fin_opt_default(smem_fin_opt_t* o) {  // mem_opt_init (software/bwamem.c:48-75)
+    std::memset(o, 0, sizeof(*o));
+    o->a = 1, o->b = 4;
+    o->o_del = o->o_ins = 6, o->e_del = o->e_ins = 1;
+    o->min_seed_len = 19, o->T = 30;
+    o->mask_level = 0.50f, o->mask_level_redun = 0.95f;
+    o->mapQ_coef_len = 50, o->mapQ_coef_fac = (int)std::log(o->mapQ_coef_len);
+}
+
+static bool fin_opt_ok(const smem_fin_opt_t* o) {
+    return o && o->a >= 1 && o->b >= 0 && o->mask_level == o->mask_level && o->mask_level_redun == o->mask_level_redun &&
+           o->mapQ_coef_len == o->mapQ_coef_len &&
+           !(o->flag & ~(SMEM_FIN_F_NO_EXACT | SMEM_FIN_F_ALL | SMEM_FIN_F_NO_MULTI));
+}
+
+// the log tables of mem_approx_mapq_se, filled with the host's libm once per handle: the
+// device's MAPQ must not depend on a device log()
+static int fin_tables(smem_gpu_t* g) {
+    std::lock_guard<std::mutex> lk(g->fin_mu);
+    if (g->d_fin_log) return SMEM_OK;
+    std::vector<double> lg(smem::FIN_TAB_LEN);
+    std::vector<int32_t> sn(smem::FIN_TAB_LEN);
+    for (int x = 0; x < smem::FIN_TAB_LEN; ++x) {
+        lg[(size_t)x] = x > 0 ? std::log((double)x) : 0.;
+        sn[(size_t)x] = (int)(4.343 * std::log((double)(x + 1)) + .499);
+    }
+    double* dl = nullptr;
+    int32_t* ds = nullptr;
+    hipError_t e = hipMalloc(&dl, sizeof(double) * lg.size());
+    if (e == hipSuccess) e = hipMalloc(&ds, sizeof(int32_t) * sn.size());
+    if (e == hipSuccess) e = hipMemcpy(dl, lg.data(), sizeof(double) * lg.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ds, sn.data(), sizeof(int32_t) * sn.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (dl) (void)hipFree(dl);
+        if (ds) (void)hipFree(ds);
+        return fail(SMEM_E_DEVICE, "finalize: log tables", e);
+    }
+    g->d_fin_subn = ds;
+    g->d_fin_log = dl;
+    return SMEM_OK;
+}
+
+// device buffers of the stage for n_reads reads of n_regs raw regions in all
+static int fin_bufs_size(FinBufs& F, uint64_t n_reads, uint64_t n_regs) {
+    const uint64_t R = std::max<uint64_t>(n_reads, 1), N = std::max<uint64_t>(n_regs, 1);
+    HIP_TRY(F.ctr.grow(4));
+    HIP_TRY(F.lane_list.grow(R));
+    HIP_TRY(F.wave_list.grow(R));
+    HIP_TRY(F.n_out.grow(R));
+    HIP_TRY(F.n_sel.grow(R));
+    HIP_TRY(F.status.grow(R));
+    HIP_TRY(F.out_off.grow(R + 1));
+    HIP_TRY(F.sel_off.grow(R + 1));
+    HIP_TRY(F.tmp_regs.grow(N));
+    HIP_TRY(F.tmp_sel.grow(N));
+    HIP_TRY(F.tmp_idx.grow(N));
+    HIP_TRY(F.out_regs.grow(N));
+    HIP_TRY(F.out_sel.grow(N));
+    HIP_TRY(F.out_idx.grow(N));
+    size_t tmp = 0;
+    HIP_TRY(smem_launch_offsets(nullptr, nullptr, (int)R, nullptr, &tmp, nullptr));
+    HIP_TRY(F.scan_tmp.grow(tmp + 256));
+    return SMEM_OK;
+}
+
+static void fin_params(smem::FinParams& P, smem_gpu_t* g, FinBufs& F, const smem_fin_opt_t* o, int n_reads,
+                       uint64_t n_regs, int64_t id0) {
+    P.id0 = id0, P.n_reads = n_reads, P.n_regs = n_regs;
+    P.a = o->a, P.b = o->b, P.o_del = o->o_del, P.e_del = o->e_del, P.o_ins = o->o_ins, P.e_ins = o->e_ins;
+    P.min_seed_len = o->min_seed_len, P.T = o->T;
+    P.mask_level = o->mask_level, P.mask_level_redun = o->mask_level_redun, P.mapQ_coef_len = o->mapQ_coef_len;
+    P.mapQ_coef_fac = o->mapQ_coef_fac;
+    P.no_exact = !!(o->flag & SMEM_FIN_F_NO_EXACT), P.all = !!(o->flag & SMEM_FIN_F_ALL);
+    P.no_multi = !!(o->flag & SMEM_FIN_F_NO_MULTI);
+    P.log_tab = g->d_fin_log, P.subn_tab = g->d_fin_subn;
+    P.ctr = F.ctr.p, P.lane_list = F.lane_list.p, P.wave_list = F.wave_list.p;
+    P.n_out = F.n_out.p, P.n_sel = F.n_sel.p, P.status = F.status.p;
+    P.tmp_regs = F.tmp_regs.p, P.tmp_sel = F.tmp_sel.p, P.tmp_idx = F.tmp_idx.p;
+    P.out_off = F.out_off.p, P.sel_off = F.sel_off.p;
+    P.out_regs = F.out_regs.p, P.out_sel = F.out_sel.p, P.out_idx = F.out_idx.p;
+}
+
+// enqueue the stage on st: split, the two tiers, the two scans, the write; ev[0..4] around them
+static int run_fin(const smem::FinParams& P, FinBufs& F, hipEvent_t* ev, hipStream_t st) {
+    const int n = P.n_reads;
+    HIP_TRY(hipMemsetAsync(F.ctr.p, 0, 4 * sizeof(uint32_t), st));
+    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(smem_launch_fin_split(&P, st));
+    HIP_TRY(hipEventRecord(ev[1], st));
+    HIP_TRY(smem_launch_fin_lane(&P, st));
+    HIP_TRY(hipEventRecord(ev[2], st));
+    HIP_TRY(smem_launch_fin_wave(&P, st));
+    HIP_TRY(hipEventRecord(ev[3], st));
+    size_t tmp = F.scan_tmp.n;
+    HIP_TRY(smem_launch_offsets(F.n_out.p, F.out_off.p, n, F.scan_tmp.p, &tmp, st));
+    tmp = F.scan_tmp.n;
+    HIP_TRY(smem_launch_offsets(F.n_sel.p, F.sel_off.p, n, F.scan_tmp.p, &tmp, st));
+    HIP_TRY(smem_launch_fin_write(&P, st));
+    HIP_TRY(hipEventRecord(ev[4], st));
+    return SMEM_OK;
+}
+
+int smem_reg_finalize(smem_gpu_t* g, int n_reads, const int* read_len, const smem_alnreg_t* regs,
+                      const uint64_t* reg_off, const int64_t* ids, int64_t id0, const smem_fin_opt_t* opt,
+                      smem_alnreg_t* regs_out, uint64_t* out_off, smem_fin_sel_t* sel, uint64_t* sel_idx,
+                      uint64_t* sel_off, int32_t* status, double* kernel_ms) {
+    g_err[0] = 0;
+    if (!g || n_reads < 0 || !out_off || !sel_off || (n_reads > 0 && (!read_len || !reg_off)))
+        return fail(SMEM_E_ARG, "smem_reg_finalize: bad arguments");
+    if (!fin_opt_ok(opt)) return fail(SMEM_E_ARG, "smem_reg_finalize: options need a >= 1, b >= 0 and known flags");
+    if (kernel_ms) *kernel_ms = 0.0;
+    out_off[0] = sel_off[0] = 0;
+    if (n_reads == 0) return SMEM_OK;
+    for (int r = 0; r < n_reads; ++r) {
+        if (reg_off[r + 1] < reg_off[r]) return fail(SMEM_E_ARG, "smem_reg_finalize: reg_off not ascending");
+        if (read_len[r] < 0) return fail(SMEM_E_ARG, "smem_reg_finalize: negative read length");
+    }
+    const uint64_t r0 = reg_off[0], n_regs = reg_off[n_reads] - r0;
+    if (n_regs >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_reg_finalize: too many regions");
+    if (n_regs > 0 && (!regs || !regs_out || !sel || !sel_idx))
+        return fail(SMEM_E_ARG, "smem_reg_finalize: no region / output buffer");
+    for (uint64_t k = 0; k < n_regs; ++k)
+        if (regs[r0 + k].qe < regs[r0 + k].qb) return fail(SMEM_E_ARG, "smem_reg_finalize: a region with qe < qb");
+    DevBuf<smem::AlnReg> dregs;
+    DevBuf<uint64_t> dregoff;
+    DevBuf<int32_t> dlen;
+    DevBuf<int64_t> dids;
+    FinBufs F;
+    HostBuf<uint64_t> htot;
+    std::vector<uint64_t> off0;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct Guard {
+        std::function<void()> f;
+        ~Guard() { f(); }
+    } guard{[&] {
+        dregs.release(); dregoff.release(); dlen.release(); dids.release(); F.release(); htot.release();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }};
+    DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
+    if (call.rc) return call.rc;
+    const hipStream_t st = call.st;
+    if (int rc = fin_tables(g)) return rc;
+    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(dregs.ensure(n_regs));
+    HIP_TRY(dregoff.ensure((uint64_t)n_reads + 1));
+    HIP_TRY(dlen.ensure((uint64_t)n_reads));
+    if (ids) HIP_TRY(dids.ensure((uint64_t)n_reads));
+    HIP_TRY(htot.ensure(2));
+    if (int rc = fin_bufs_size(F, (uint64_t)n_reads, n_regs)) return rc;
+    const uint64_t* h_off = reg_off;
+    if (r0) {  // the kernels index regs from 0
+        off0.resize((size_t)n_reads + 1);
+        for (int r = 0; r <= n_reads; ++r) off0[(size_t)r] = reg_off[r] - r0;
+        h_off = off0.data();
+    }
+    if (n_regs) HIP_TRY(hipMemcpyAsync(dregs.p, regs + r0, sizeof(smem::AlnReg) * n_regs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dregoff.p, h_off, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dlen.p, read_len, sizeof(int32_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
+    if (ids) HIP_TRY(hipMemcpyAsync(dids.p, ids, sizeof(int64_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
+    smem::FinParams P;
+    std::memset(&P, 0, sizeof(P));
+    fin_params(P, g, F, opt, n_reads, n_regs, id0);
+    P.regs = dregs.p, P.reg_off = dregoff.p, P.read_len = dlen.p, P.ids = ids ? dids.p : nullptr;
+    if (int rc = run_fin(P, F, ev, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(htot.p, F.out_off.p + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(htot.p + 1, F.sel_off.p + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    INJECT(ST_FIN);
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t n_out = htot.p[0], n_sel = htot.p[1];
+    if (n_out > n_regs || n_sel > n_out) return fail(SMEM_E_INTERNAL, "smem_reg_finalize: more regions out than in");
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[4]));
+    if (kernel_ms) *kernel_ms = ms;
+    HIP_TRY(hipMemcpyAsync(out_off, F.out_off.p, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sel_off, F.sel_off.p, sizeof(uint64_t) * ((size_t)n_reads + 1), hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(hipMemcpyAsync(status, F.status.p, sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
+    if (n_out) {
+        HIP_TRY(hipMemcpyAsync(regs_out, F.out_regs.p, sizeof(smem::AlnReg) * n_out, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(sel, F.out_sel.p, sizeof(smem::FinSel) * n_out, hipMemcpyDeviceToHost, st));
+    }
+    if (n_sel) HIP_TRY(hipMemcpyAsync(sel_idx, F.out_idx.p, sizeof(uint64_t) * n_sel, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SMEM_OK;
+}
+
+int smem_batch_reg_finalize(smem_batch_t* b, const int64_t* ids, int64_t id0, const smem_fin_opt_t* opt) {
+    g_err[0] = 0;
+    if (!b || !b->aln_ran) return fail(SMEM_E_ARG, "smem_batch_reg_finalize: run smem_batch_chain2aln first");
+    if (!fin_opt_ok(opt)) return fail(SMEM_E_ARG, "smem_batch_reg_finalize: options need a >= 1, b >= 0 and known flags");
+    smem_gpu_t* g = b->g;
+    BatchCall call(b);
+    if (call.rc) return call.rc;
+    b->fin_ran = b->fin_fetched = false;
+    g->fin_used.store(true);  // slots reserved from now on carry the stage's buffers
+    const int n = b->n_reads;
+    if (int rc = fin_tables(g)) return rc;
+    if (int rc = fin_bufs_size(b->fin, (uint64_t)n, b->tot_regs)) return rc;
+    if (ids) {
+        HIP_TRY(b->fin.ids.grow((uint64_t)std::max(n, 1)));
+        HIP_TRY(b->h_fin_ids.grow((uint64_t)std::max(n, 1)));  // pinned: the copy is asynchronous
+        std::memcpy(b->h_fin_ids.p, ids, sizeof(int64_t) * (size_t)n);
+        HIP_TRY(hipMemcpyAsync(b->fin.ids.p, b->h_fin_ids.p, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, b->st));
+    }
+    smem::FinParams P;
+    std::memset(&P, 0, sizeof(P));
+    fin_params(P, g, b->fin, opt, n, b->tot_regs, id0);
+    P.regs = b->d_aln_out.p, P.reg_off = b->d_aln_regoff.p, P.offs = b->d_offs.p, P.ids = ids ? b->fin.ids.p : nullptr;
+    b->tot_fin = b->tot_fin_sel = 0;
+    if (n > 0) {
+        if (int rc = run_fin(P, b->fin, b->ev, b->st)) return rc;
+        HIP_TRY(hipMemcpyAsync(b->h_tot.p + 6, b->fin.out_off.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, b->st));
+        HIP_TRY(hipMemcpyAsync(b->h_tot.p + 7, b->fin.sel_off.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, b->st));
+    }
+    INJECT(ST_FIN);
+    HIP_TRY(hipStreamSynchronize(b->st));
+    if (n > 0) {
+        b->tot_fin = b->h_tot.p[6], b->tot_fin_sel = b->h_tot.p[7];
+        if (b->tot_fin > b->tot_regs || b->tot_fin_sel > b->tot_fin)
+            return fail(SMEM_E_INTERNAL, "smem_batch_reg_finalize: more regions out than in");
+        float ms = 0.f, ms_lane = 0.f, ms_wave = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[4]));
+        HIP_TRY(hipEventElapsedTime(&ms_lane, b->ev[1], b->ev[2]));
+        HIP_TRY(hipEventElapsedTime(&ms_wave, b->ev[2], b->ev[3]));
+        b->stats.fin_ms = ms, b->stats.fin_lane_ms = ms_lane, b->stats.fin_wave_ms = ms_wave;
+    }
+    b->stats.n_fin = b->tot_fin, b->stats.n_fin_sel = b->tot_fin_sel;
+    b->fin_ran = true;
+    return SMEM_OK;
+}
+
+int smem_batch_fin_results(const smem_batch_t* b, const smem_alnreg_t** regs_out, const uint64_t** out_off,
+                           const smem_fin_sel_t** sel, const uint64_t** sel_idx, const uint64_t** sel_off,
+                           const int32_t** status, uint64_t* n_out, uint64_t* n_sel) {
+    if (!b || !b->fin_fetched) return SMEM_E_ARG;
+    if (regs_out) *regs_out = reinterpret_cast<const smem_alnreg_t*>(b->h_fin_regs.p);
+    if (out_off) *out_off = b->h_fin_off.p;
+    if (sel) *sel = reinterpret_cast<const smem_fin_sel_t*>(b->h_fin_sel.p);
+    if (sel_idx) *sel_idx = b->h_fin_idx.p;
+    if (sel_off) *sel_off = b->h_fin_off.p + (b->n_reads + 1);
+    if (status) *status = b->h_fin_status.p;
+    if (n_out) *n_out = b->tot_fin;
+    if (n_sel) *n_sel = b->tot_fin_sel;
+    return SMEM_OK;
+}
+
 int smem_batch_stats(const smem_batch_t* b, smem_batch_stats_t* st) {
     if (!b || !st) return SMEM_E_ARG;
     *st = b->stats;
@@ -3009,6 +3333,7 @@ static int collect_batch(smem_gpu_t* g, int slot, int n_reads, int max_len, uint
 // 48 / 24 / 8 / 16 per read held 38.6 GB and took 0.43 s to free.)
 // (no device work here or in smem_batch_create: smem_gpu_reserve_slots runs
 // both once with a measuring Arena, whose buffers are placeholders)
+static int fin_bufs_size(FinBufs& F, uint64_t n_reads, uint64_t n_regs);
 static int batch_prealloc(smem_batch_t* b) {
     const uint64_t R = (uint64_t)b->max_reads;
     const uint64_t ni = R * 40, no = R * 16, nc = R * 6, ns = R * 12;
@@ -3040,6 +3365,8 @@ static int batch_prealloc(smem_batch_t* b) {
     HIP_TRY(b->d_aln_nregs.grow(R));
     HIP_TRY(b->d_aln_regoff.grow(R + 1));
     HIP_TRY(b->d_aln_ctr.grow(smem::ALN_CTRS));
+    if (b->g->fin_used.load())  // only where the stage is in use
+        if (int rc = fin_bufs_size(b->fin, R, ns)) return rc;
     AlnHeavyBufs& H = b->aln_heavy;
     HIP_TRY(H.pre.grow(ns));
     HIP_TRY(H.pre_ok.grow(ns));

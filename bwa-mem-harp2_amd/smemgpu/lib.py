@@ -38,10 +38,12 @@ EXPORTED = [
     "smem_batch_memory", "smem_gpu_memory", "smem_gpu_init_devices_async", "smem_gpu_wait_ready",
     "smem_gpu_open_async", "smem_gpu_load_sa_async", "smem_gpu_load_pac_async",
     "smem_reg2aln",
+    "smem_fin_opt_default", "smem_reg_finalize", "smem_batch_reg_finalize", "smem_batch_fin_results",
 ]
 
 # smem_batch_fetch_mask bits (include/smem_gpu.h)
 FETCH_INTV, FETCH_SA, FETCH_CHAINS, FETCH_REGS, FETCH_ALL = 1, 2, 4, 8, 15
+FETCH_FIN = 16   # Batch.reg_finalize's results; not part of FETCH_ALL
 COLLECT_NO_FETCH = 1
 
 
@@ -101,7 +103,9 @@ class BatchStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("compact_ms", C.c_double), ("n_intv", C.c_uint64),
                 ("n_calls", C.c_uint64), ("n_overflow", C.c_uint32), ("grid", C.c_int), ("block", C.c_int),
                 ("sa_ms", C.c_double), ("n_occ", C.c_uint64), ("chain_ms", C.c_double), ("n_chains", C.c_uint64),
-                ("aln_ms", C.c_double), ("n_regs", C.c_uint64), ("t_start", C.c_uint64), ("t_end", C.c_uint64)]
+                ("aln_ms", C.c_double), ("n_regs", C.c_uint64), ("t_start", C.c_uint64), ("t_end", C.c_uint64),
+                ("fin_ms", C.c_double), ("fin_lane_ms", C.c_double), ("fin_wave_ms", C.c_double),
+                ("n_fin", C.c_uint64), ("n_fin_sel", C.c_uint64)]
 
 
 class StreamStats(C.Structure):
@@ -143,6 +147,32 @@ def aln_opt(**kw) -> AlnOptT:
     return o
 
 
+class FinOptT(C.Structure):
+    """smem_fin_opt_t: the mem_opt_t fields raw regions -> final regions reads"""
+    _fields_ = [("a", C.c_int), ("b", C.c_int), ("o_del", C.c_int), ("e_del", C.c_int), ("o_ins", C.c_int),
+                ("e_ins", C.c_int), ("min_seed_len", C.c_int), ("T", C.c_int), ("mask_level", C.c_float),
+                ("mask_level_redun", C.c_float), ("mapQ_coef_len", C.c_float), ("mapQ_coef_fac", C.c_int),
+                ("flag", C.c_int)]
+
+
+FIN_F_NO_EXACT, FIN_F_ALL, FIN_F_NO_MULTI = 1, 2, 4
+FIN_MAX_REGS, FIN_TAB_LEN, FIN_REJECT = 1024, 4096, 1
+
+
+def fin_opt(**kw) -> FinOptT:
+    """smem_fin_opt_default (mem_opt_init, software/bwamem.c:48-75) with the
+    named fields overridden; no_exact / all / no_multi set the flag bits."""
+    o = FinOptT()
+    load().smem_fin_opt_default(C.byref(o))
+    for k, v in kw.items():
+        if k in ("no_exact", "all", "no_multi"):
+            bit = {"no_exact": FIN_F_NO_EXACT, "all": FIN_F_ALL, "no_multi": FIN_F_NO_MULTI}[k]
+            o.flag = (o.flag | bit) if v else (o.flag & ~bit)
+        else:
+            setattr(o, k, v)
+    return o
+
+
 SEED_DT = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4")])          # smem_seed_t = mem_seed_t
 CHAIN_DT = np.dtype([("pos", "<i8"), ("seed_off", "<u8"), ("n", "<i4"), ("pad", "<i4")])  # smem_chain_t
 # smem_alnreg_t = mem_alnreg_t (the 64-byte records chain2aln returns)
@@ -154,6 +184,7 @@ ALN_DT = np.dtype([("pos", "<i8"), ("is_rev", "<i4"), ("n_cigar", "<i4"), ("NM",
                    ("tries", "<i4"), ("status", "<i4"), ("cigar_off", "<u8"), ("md_off", "<u8"), ("md_len", "<i4"),
                    ("pad", "<i4")])
 ALN_UNMAPPED, ALN_NOCIGAR, ALN_REJECT = 1, 2, 3
+FIN_SEL_DT = np.dtype([("mapq", "<i4"), ("flag", "<i4"), ("xs", "<i4")])   # smem_fin_sel_t
 SMEM_E_CAPACITY = -6
 
 
@@ -198,6 +229,15 @@ def load() -> C.CDLL:
     lib.smem_reg2aln.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_uint64),
                                  C.c_void_p, C.c_uint64, P(C.c_uint64), P(C.c_double)]
+    lib.smem_fin_opt_default.argtypes = [P(FinOptT)]
+    lib.smem_fin_opt_default.restype = None
+    lib.smem_reg_finalize.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                      P(FinOptT), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, P(C.c_double)]
+    lib.smem_batch_reg_finalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(FinOptT)]
+    lib.smem_batch_fin_results.argtypes = [C.c_void_p, P(C.c_void_p), P(P(C.c_uint64)), P(C.c_void_p),
+                                           P(P(C.c_uint64)), P(P(C.c_uint64)), P(P(C.c_int32)), P(C.c_uint64),
+                                           P(C.c_uint64)]
     lib.smem_chain_opt_default.argtypes = [P(ChainOptT)]
     lib.smem_chain_opt_default.restype = None
     lib.smem_batch_chain.argtypes = [C.c_void_p, C.c_int64, P(ChainOptT)]
@@ -405,6 +445,18 @@ def device_count() -> int:
 
 
 @dataclass
+class FinResults:
+    """raw regions -> final regions (smem_reg_finalize / smem_batch_reg_finalize)"""
+    regs: np.ndarray      # ALNREG_DT: every read's final list, in mem_mark_primary_se's order
+    out_off: np.ndarray   # (n_reads + 1,) uint64 into regs / sel
+    sel: np.ndarray       # FIN_SEL_DT, one per final region; flag -1: no record
+    sel_idx: np.ndarray   # uint64: the regions with a record, per read in print order, as indices into regs
+    sel_off: np.ndarray   # (n_reads + 1,) uint64 into sel_idx
+    status: np.ndarray    # (n_reads,) int32: 0 or FIN_REJECT
+    kernel_ms: float = 0.0
+
+
+@dataclass
 class Results:
     intv: np.ndarray      # (N, 4) uint64: x0, x1, x2, info
     intv_off: np.ndarray  # (n_reads + 1,) uint64
@@ -417,6 +469,7 @@ class Results:
     seeds: np.ndarray | None = None    # SEED_DT, each chain's seeds contiguous
     regs: np.ndarray | None = None     # raw 64-byte smem_alnreg_t records, when Batch.chain2aln() ran
     reg_off: np.ndarray | None = None  # (n_reads + 1,) uint64
+    fin: "FinResults | None" = None    # when Batch.reg_finalize() ran and FETCH_FIN was asked for
 
     def read_chains(self, i: int) -> list:
         """read i's chains as [(pos, seeds)], in mem_chain(+flt) order."""
@@ -710,6 +763,42 @@ class Gpu:
             _check(rc, "smem_reg2aln")
             return alns[:n_regs], cigar[:int(nc.value)], md[:int(nm.value)], ms.value
 
+    def reg_finalize(self, read_len, regs, reg_off, opt: FinOptT = None, ids=None, id0: int = 0) -> FinResults:
+        """mem_sort_and_dedup, mem_mark_primary_se and the selection, MAPQ and
+        flags of mem_reg2sam_se for every read's raw regions (smem_reg_finalize):
+        regs as ALNREG_DT (or the raw bytes chain2aln returns), reg_off their
+        reads, read_len the reads' lengths, ids the per-read hash ids (None:
+        id0 + r).  regs[sel_idx] of the result is reg2aln's input."""
+        lib = load()
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.uint64)
+        regs = np.ascontiguousarray(regs)
+        if regs.dtype != ALNREG_DT:
+            regs = np.frombuffer(regs.astype(np.uint8, copy=False).tobytes(), dtype=ALNREG_DT)
+        n = read_len.size
+        if reg_off.size != n + 1 or int(reg_off[-1]) > regs.size:
+            raise SmemError("reg_finalize: reg_off must have n_reads + 1 entries within regs")
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            if ids.size != n:
+                raise SmemError("reg_finalize: one id per read")
+        if opt is None:
+            opt = fin_opt()
+        cap = max(int(reg_off[-1]), 1)
+        out = np.zeros(cap, dtype=ALNREG_DT)
+        sel = np.zeros(cap, dtype=FIN_SEL_DT)
+        sel_idx = np.zeros(cap, dtype=np.uint64)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        sel_off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ms = C.c_double()
+        _check(lib.smem_reg_finalize(self._h, n, read_len.ctypes.data, regs.ctypes.data, reg_off.ctypes.data,
+                                     ids.ctypes.data if ids is not None else None, int(id0), C.byref(opt),
+                                     out.ctypes.data, out_off.ctypes.data, sel.ctypes.data, sel_idx.ctypes.data,
+                                     sel_off.ctypes.data, status.ctypes.data, C.byref(ms)), "smem_reg_finalize")
+        no, ns = int(out_off[-1]), int(sel_off[-1])
+        return FinResults(out[:no], out_off, sel[:no], sel_idx[:ns], sel_off, status[:n], ms.value)
+
     def close(self) -> None:
         if self._h:
             load().smem_gpu_shutdown(self._h)
@@ -773,6 +862,19 @@ class Batch:
         (smem_batch_chain2aln); opt is laid out as smem_aln_opt_t."""
         _check(load().smem_batch_chain2aln(self._h, C.byref(opt)), "smem_batch_chain2aln")
 
+    def reg_finalize(self, opt: FinOptT = None, ids=None, id0: int = 0) -> None:
+        """Raw regions -> final regions, marks, selection, MAPQ and flags of
+        every read of the last chain2aln(), over the regions in HBM
+        (smem_batch_reg_finalize); fetch(FETCH_FIN) returns them as .fin."""
+        if opt is None:
+            opt = fin_opt()
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            if ids.size != self.n_reads:
+                raise SmemError("reg_finalize: one id per read")
+        _check(load().smem_batch_reg_finalize(self._h, ids.ctypes.data if ids is not None else None, int(id0),
+                                              C.byref(opt)), "smem_batch_reg_finalize")
+
     def debug_words(self, n_words: int) -> np.ndarray:
         out = np.zeros(n_words, dtype=np.uint64)
         rc = load().smem_batch_debug(self._h, out.ctypes.data, n_words)
@@ -820,6 +922,20 @@ class Batch:
             k = int(nr.value)
             res.reg_off = np.ctypeslib.as_array(ro, shape=(n + 1,)).copy()
             res.regs = np.frombuffer((C.c_char * (max(k, 1) * 64)).from_address(rg.value), dtype=np.uint8)[:k * 64].copy()
+        fr, fs = C.c_void_p(), C.c_void_p()
+        fo, fi, fso = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        fst = C.POINTER(C.c_int32)()
+        nf, nfs = C.c_uint64(), C.c_uint64()
+        if lib.smem_batch_fin_results(self._h, C.byref(fr), C.byref(fo), C.byref(fs), C.byref(fi), C.byref(fso),
+                                      C.byref(fst), C.byref(nf), C.byref(nfs)) == 0:
+            k, ks = int(nf.value), int(nfs.value)
+            res.fin = FinResults(
+                np.frombuffer((C.c_char * (max(k, 1) * 64)).from_address(fr.value), dtype=ALNREG_DT)[:k].copy(),
+                np.ctypeslib.as_array(fo, shape=(n + 1,)).copy(),
+                np.frombuffer((C.c_char * (max(k, 1) * 12)).from_address(fs.value), dtype=FIN_SEL_DT)[:k].copy(),
+                np.ctypeslib.as_array(fi, shape=(max(ks, 1),))[:ks].copy(),
+                np.ctypeslib.as_array(fso, shape=(n + 1,)).copy(),
+                np.ctypeslib.as_array(fst, shape=(max(n, 1),))[:n].copy(), self.stats()["fin_ms"])
         return res
 
     def close(self) -> None:

@@ -28,7 +28,7 @@
  * caller that takes its CPU path on SMEM_E_DEVICE computes exactly what the
  * reference computes.  Allocation failures are SMEM_E_NOMEM and leave the
  * device usable.  SMEM_GPU_FAIL=<stage>:<k>[:sticky] (stage: upload, seed,
- * sa, chain, aln, fetch, any) injects SMEM_E_DEVICE into every k-th call of
+ * sa, chain, aln, fin, fetch, any) injects SMEM_E_DEVICE into every k-th call of
  * the stage after its work is enqueued, to test that contract.
  */
 #ifndef SMEM_GPU_H
@@ -299,6 +299,7 @@ int  smem_batch_fetch(smem_batch_t *b);
 #define SMEM_FETCH_CHAINS  4
 #define SMEM_FETCH_REGS    8
 #define SMEM_FETCH_ALL    15
+#define SMEM_FETCH_FIN    16   /* smem_batch_reg_finalize's results (smem_batch_fin_results); not part of ALL */
 int  smem_batch_fetch_mask(smem_batch_t *b, int mask);
 /* per-read view of fetched results: the concatenation of all smem_next2
  * lists in order (n_intv intervals) and the size of each list (n_calls) */
@@ -525,6 +526,64 @@ int  smem_reg2aln(smem_gpu_t *gpu, int n_reads, const uint8_t *codes, const uint
                   smem_aln_t *alns, uint32_t *cigar, uint64_t cigar_cap, uint64_t *n_cigar_words,
                   char *md, uint64_t md_cap, uint64_t *n_md_bytes, double *kernel_ms);
 
+/* ------------------------------------------- raw regions -> final regions */
+/* the mem_opt_t fields the stage reads (software/bwamem.h:33-58) */
+typedef struct {
+	int a, b;                          /* 1, 4 */
+	int o_del, e_del, o_ins, e_ins;    /* 6, 1, 6, 1 */
+	int min_seed_len;                  /* 19 */
+	int T;                             /* 30: minimum score to output */
+	float mask_level;                  /* 0.50 */
+	float mask_level_redun;            /* 0.95 */
+	float mapQ_coef_len;               /* 50 */
+	int mapQ_coef_fac;                 /* (int)log(50) = 3: an int in the reference (software/bwamem.h:56) */
+	int flag;                          /* SMEM_FIN_F_* */
+} smem_fin_opt_t;
+#define SMEM_FIN_F_NO_EXACT 1          /* MEM_F_NO_EXACT: mem_test_and_remove_exact runs */
+#define SMEM_FIN_F_ALL      2          /* MEM_F_ALL: secondary regions get records */
+#define SMEM_FIN_F_NO_MULTI 4          /* MEM_F_NO_MULTI: 0x10000 instead of 0x800 */
+void smem_fin_opt_default(smem_fin_opt_t *opt);
+/* what mem_reg2sam_se / mem_reg2aln decide about one final region before they align it
+ * (software/bwamem.c:1370-1379, 1498-1499, 1550): flag -1: the region gets no record; else the
+ * bits 0x100 (secondary), 0x800 or 0x10000 (supplementary) -- 0x10 is the strand of rb, the
+ * caller's; mapq after the cap at the read's first record, or -1: an argument of
+ * mem_approx_mapq_se lies outside the stage's tables (max(qe - qb, re - rb), seedcov or sub_n
+ * >= SMEM_FIN_TAB_LEN, seedcov < 1 where its log is needed, a region of length 0) and the
+ * caller computes it -- the cap applies to -1 as to any number, so the records behind a first
+ * record of -1 are -1 too; xs = max(sub, csub), -1 for a secondary region */
+typedef struct { int32_t mapq, flag, xs; } smem_fin_sel_t;
+#define SMEM_FIN_MAX_REGS 1024         /* raw regions of one read */
+#define SMEM_FIN_TAB_LEN  4096
+#define SMEM_FIN_REJECT   1
+/* mem_sort_and_dedup (software/bwamem.c:705-746), mem_test_and_remove_exact (:748-753, with
+ * SMEM_FIN_F_NO_EXACT), mem_mark_primary_se (:755-785) and the selection, MAPQ and flags at
+ * the head of mem_reg2sam_se / mem_reg2aln, of every read on the GPU.  Host buffers in and
+ * out.  regs[reg_off[r] .. reg_off[r+1]) are the raw regions of read r in the order
+ * mem_chain2aln appended them (smem_chain2aln's output as it is), read_len[r] its length,
+ * ids[r] the id its hashes start from (NULL: id0 + r; single-end n_processed + r, paired-end
+ * id << 1 | end, software/bwamem.c:1604, software/bwamem_pair.c:264-265).
+ * regs_out (room for reg_off[n_reads] regions) / out_off[n_reads + 1]: each read's final list
+ * in mem_mark_primary_se's order with sub, sub_n (added to the incoming value, as the
+ * reference does), secondary (an index within the read's list, -1: primary) and hash set;
+ * sel: one per output region; sel_idx (room for reg_off[n_reads]) / sel_off[n_reads + 1]:
+ * the regions that get a record, per read in print order, as indices into regs_out -- a read
+ * with none gets the caller's unmapped record.  regs_out[sel_idx[..]] is smem_reg2aln's input.
+ * status[r] (may be NULL): 0, or SMEM_FIN_REJECT for a read of more than SMEM_FIN_MAX_REGS
+ * raw regions: it gets an empty list, the call goes on and the caller does that read on the
+ * CPU.  SMEM_E_ARG: reg_off not ascending, a region with qe < qb, a negative read length. */
+int  smem_reg_finalize(smem_gpu_t *gpu, int n_reads, const int *read_len, const smem_alnreg_t *regs,
+                       const uint64_t *reg_off, const int64_t *ids, int64_t id0, const smem_fin_opt_t *opt,
+                       smem_alnreg_t *regs_out, uint64_t *out_off, smem_fin_sel_t *sel, uint64_t *sel_idx,
+                       uint64_t *sel_off, int32_t *status, double *kernel_ms);
+/* Device-resident twin: after smem_batch_chain2aln, over the regions still in HBM (no host
+ * round trip).  smem_batch_fetch_mask(b, SMEM_FETCH_FIN) copies the results, smem_batch_fin_results
+ * returns them (any pointer may be NULL); SMEM_FETCH_REGS keeps returning the raw regions.  The
+ * stage's buffers exist only in a batch that called it; smem_batch_stats' fin_ms is its kernel time. */
+int  smem_batch_reg_finalize(smem_batch_t *b, const int64_t *ids, int64_t id0, const smem_fin_opt_t *opt);
+int  smem_batch_fin_results(const smem_batch_t *b, const smem_alnreg_t **regs_out, const uint64_t **out_off,
+                            const smem_fin_sel_t **sel, const uint64_t **sel_idx, const uint64_t **sel_off,
+                            const int32_t **status, uint64_t *n_out, uint64_t *n_sel);
+
 /* ---------------------------------------------------------- telemetry */
 typedef struct {
 	double kernel_ms;        /* seeding kernel(s), HIP events on the batch stream */
@@ -541,6 +600,9 @@ typedef struct {
 	uint64_t n_regs;         /* regions made by smem_batch_chain2aln */
 	uint64_t t_start, t_end; /* the seeding launches' first wave start and last wave end, chip-wide
 	                          * 100 MHz clock (s_memrealtime): comparable across batches and streams */
+	double fin_ms;           /* smem_batch_reg_finalize kernels; fin_lane_ms / fin_wave_ms: its two tiers */
+	double fin_lane_ms, fin_wave_ms;
+	uint64_t n_fin, n_fin_sel; /* final regions, regions with a record */
 } smem_batch_stats_t;
 int  smem_batch_stats(const smem_batch_t *b, smem_batch_stats_t *st);
 
