@@ -268,7 +268,7 @@ constexpr int kSeedDefault = 49;
 static int seed_lanes_per_cu(int variant) {
     switch (variant) {
         case 44: case 45: case 46: case 49: case 50: case 51: case 52: case 53: case 54: case 56: case 57:
-        case 58: case 59: case 60: case 61: case 62: return 960;
+        case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: return 960;
         default: return 768;
     }
 }
@@ -278,7 +278,7 @@ static int seed_owners_per_wave(int variant) {
     switch (variant) {
         case 40: case 41: case 43: case 45: case 47: case 55: return 32;
         case 42: case 44: case 48: case 49: case 51: case 52: case 54: case 56: case 57:
-        case 58: case 59: case 60: case 61: case 62: return 24;
+        case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: return 24;
         case 46: case 53: return 28;
         case 50: return 20;
         default: return 64;
@@ -289,12 +289,7 @@ static int seed_lanes_per_read(int variant) { return (64 + seed_owners_per_wave(
 // list arenas a launch of `lanes` lanes addresses (2 x cap_list packed entries each): seed_wp_kernel
 // one per owner (OWN a wave), seed_kernel one per lane
 static size_t seed_arenas(int variant, int lanes) {
-#ifdef SMEM_WP_ARENA_PER_LANE
-    (void)variant;
-    return (size_t)lanes;
-#else
     return variant >= 40 ? (size_t)(lanes / 64) * (size_t)seed_owners_per_wave(variant) : (size_t)lanes;
-#endif
 }
 
 struct smem_gpu {
@@ -840,7 +835,7 @@ int smem_gpu_set_lanes_per_cu(smem_gpu_t* g, int lanes_per_cu) {
 
 int smem_gpu_set_kernel_variant(smem_gpu_t* g, int variant) {
     g_err[0] = 0;
-    if (!g || !(variant == 0 || (variant >= 2 && variant <= 31) || (variant >= 40 && variant <= 62)))
+    if (!g || !(variant == 0 || (variant >= 2 && variant <= 31) || (variant >= 40 && variant <= 67)))
         return fail(SMEM_E_ARG, "smem_gpu_set_kernel_variant");
 
     if (!smem_seed_variant_built(variant))

@@ -31,40 +31,17 @@
 
 namespace smem {
 
-// one 64-B Occ bucket: 4 x u64 checkpoint, 8 x u32 of 16 MSB-first 2-bit symbols
-struct Bucket {
-    uint4 c01, c23, w03, w47;
-};
-
-// Counts of C, G, T among the first pos+1 symbols of the bucket's 8 words
-// (MSB-first 2-bit symbols). A = pos+1 - C - G - T, which is what
-// bwt_occ4's "masked tail reads as A, subtract ~k&15" produces.
-__device__ __forceinline__ void count_cgt(const Bucket& v, uint32_t pos, uint32_t& C, uint32_t& G, uint32_t& T) {
-    const uint32_t w[8] = {v.w03.x, v.w03.y, v.w03.z, v.w03.w, v.w47.x, v.w47.y, v.w47.z, v.w47.w};
-    const uint32_t nfull = pos >> 4;
-    const uint32_t tail = ~((1u << ((15u - (pos & 15u)) << 1)) - 1u);
-    uint32_t sT = 0, sLo = 0, sHi = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 8; ++i) {
-        const uint32_t m = i < nfull ? 0xFFFFFFFFu : (i == nfull ? tail : 0u);
-        const uint32_t x = w[i] & m;
-        const uint32_t lo = x & 0x55555555u;
-        const uint32_t hi = (x >> 1) & 0x55555555u;
-        sT += __popc(lo & hi);
-        sLo += __popc(lo);
-        sHi += __popc(hi);
-    }
-    T = sT;
-    C = sLo - sT;
-    G = sHi - sT;
-}
-
-__device__ __forceinline__ uint64_t cnt64(const uint4& v, int hi) {
-    return hi ? ((uint64_t)v.w << 32 | v.z) : ((uint64_t)v.y << 32 | v.x);
-}
-
+// one of four by a compare chain (the SA walk and the table builders; in seed_wp_kernel only the A/B
+// twin of sel4b below)
 __device__ __forceinline__ uint64_t sel4(int c, uint64_t a, uint64_t b, uint64_t d, uint64_t e) {
     return c == 0 ? a : (c == 1 ? b : (c == 2 ? d : e));
+}
+
+// sel4 as two bit tests of c (0..3): v_cndmask only, where the compare chain above becomes a branch tree
+__device__ __forceinline__ uint64_t sel4b(int c, uint64_t a, uint64_t b, uint64_t d, uint64_t e) {
+    const bool b0 = c & 1, b1 = c & 2;
+    const uint64_t lo = b0 ? b : a, hi = b0 ? e : d;
+    return b1 ? hi : lo;
 }
 
 // ---- packed list entries (forward / prev / curr lists): 16 B instead of 32 B.
@@ -78,7 +55,6 @@ __host__ __device__ __forceinline__ uint4 pack_p(uint64_t x0, uint64_t x1, uint6
                       (uint32_t)(x0 >> 32) | (uint32_t)(x1 >> 32) << 2 | (uint32_t)(x2 >> 32) << 4 | end << 6);
 }
 
-__device__ __forceinline__ uint4 load_p(const PIntv* p) { return *reinterpret_cast<const uint4*>(p); }
 __device__ __forceinline__ uint64_t p_x0(const uint4& v) { return (uint64_t)(v.w & 3) << 32 | v.x; }
 __device__ __forceinline__ uint64_t p_x1(const uint4& v) { return (uint64_t)((v.w >> 2) & 3) << 32 | v.y; }
 __device__ __forceinline__ uint64_t p_x2(const uint4& v) { return (uint64_t)((v.w >> 4) & 3) << 32 | v.z; }
@@ -86,10 +62,18 @@ __device__ __forceinline__ uint32_t p_end(const uint4& v) { return v.w >> 6; }
 
 // ---- query bases through a 16-byte window held in registers; the window
 // is loaded in the uniform section (the state machine yields until it is)
+template <bool BSEL = false>
 __device__ __forceinline__ int qsel(uint32_t o0, int i, const uint4& qv) {
     const uint32_t a = o0 + (uint32_t)i;  // batches hold < 2^32 bases
-    const uint32_t sel = (a >> 2) & 3;
-    const uint32_t w = sel == 0 ? qv.x : (sel == 1 ? qv.y : (sel == 2 ? qv.z : qv.w));
+    if constexpr (BSEL) {  // the window's half by one bit test, the byte by a 64-bit shift
+        const uint64_t h0 = (uint64_t)qv.y << 32 | qv.x, h1 = (uint64_t)qv.w << 32 | qv.z;
+        return (int)(((a & 8) ? h1 : h0) >> ((a & 7) * 8) & 0xff);
+    }
+    uint32_t w;
+    {
+        const uint32_t sel = (a >> 2) & 3;
+        w = sel == 0 ? qv.x : (sel == 1 ? qv.y : (sel == 2 ? qv.z : qv.w));
+    }
     return (int)((w >> ((a & 3) * 8)) & 0xff);
 }
 
@@ -110,50 +94,6 @@ enum Phase : int {
     P_EXIT
 };
 
-constexpr uint32_t NO_BUCKET = 0xFFFFFFFFu;
-// backward-list entries per lane kept in LDS.  On the bench workload 86 % of
-// curr pushes and 80 % of prev reads fall below 7 (99 % below 12); 7 entries
-// keep the wave at 13 KB of LDS, so 3 blocks of 4 waves fit a CU, which
-// measured faster than 12 entries at 2 blocks (39.5 vs 42.1 ms per 1M reads).
-// The forward list itself stays in global memory.
-[[maybe_unused]] constexpr int LIST_LDS = 7;
-
-// Wave-private LDS.  img: the Occ bucket image (FETCH_OCC64: 4 planes
-// [slot*2 + chunk][lane]; FETCH_LANE: 8 planes [k0..k3, l0..l3][lane];
-// FETCH_COOP: [k|l][lane][4 chunks]).  pn / q: one 16-B landing slot per lane
-// for prev[j+1] and for the query window, filled by LDS-DMA.  The first
-// NLIST entries of the lane's backward interval list (curr, which becomes
-// prev) live in WaveListT, entry-major so that a wave's accesses are
-// bank-conflict free whatever entry each lane is at.
-template <int NIMG>
-struct WaveLdsT {
-    uint4 img[NIMG][64];
-    uint4 pn[64];
-    uint4 q[64];
-};
-template <>
-struct WaveLdsT<0> {  // VSLOT: the bucket slots live in registers
-    uint4 pn[64];
-    uint4 q[64];
-};
-
-// the backward-list entries kept in LDS, per wave [entry][lane].  A separate
-// __shared__ object from the LDS-DMA targets above, so the compiler can see
-// that reading a list entry does not wait for bucket DMAs in flight.
-template <int NLIST>
-struct WaveListT {
-    uint4 e[NLIST > 0 ? NLIST : 1][64];
-};
-
-// The lane id, recomputed where it is used: the register allocator would
-// otherwise keep it (and addresses derived from it) live across the whole
-// state machine, or spill them.
-__device__ __forceinline__ int vlane() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
 // bucket b's 16-B chunk as scalar base + 32-bit byte offset (the host keeps
 // the index below 4 GiB), so the DMA takes the saddr form
 __device__ __forceinline__ const uint32_t* boff(const uint32_t* __restrict__ bwt, uint32_t b, uint32_t chunk) {
@@ -161,96 +101,6 @@ __device__ __forceinline__ const uint32_t* boff(const uint32_t* __restrict__ bwt
 }
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-enum FetchMode { FETCH_LANE = 0, FETCH_COOP = 1, FETCH_OCC64 = 2 };
-
-// Fetch the 64-B Occ buckets of k and l (l only when it is another bucket,
-// bwt_2occ4's same-bucket case) for every lane that has an extend request,
-// by LDS-DMA, and return them in registers.
-//  FETCH_COOP (default): each instruction moves 16 whole buckets (4 lanes x
-//    16 B, bucket indices exchanged by ds_bpermute).
-//  FETCH_LANE: every lane DMAs its own bucket, one 16-B chunk per
-//    instruction (8 instructions: 4 chunks x k, l), into chunk planes.
-//  On uniformly random buckets of a 1 GB table (tools/gather_ceiling.hip)
-//  FETCH_LANE reads 3.1x faster (43.6 vs 13.9 G buckets/s), but in the
-//  seeding kernel, whose accesses share upper FM-index levels, FETCH_COOP
-//  is 14 % faster (51.8 vs 60.5 ms per 1M reads, 1 Gbp): kept both for A/B.
-template <int FETCH, class WL>
-__device__ __forceinline__ void fetch_buckets(const uint32_t* __restrict__ bwt, WL* W, bool want,
-                                              uint64_t kk, uint64_t ll, Bucket& vk, Bucket& vl) {
-    const bool needl = want && (kk >> 7) != (ll >> 7);
-    if constexpr (FETCH == FETCH_LANE) {
-        const uint32_t bk = (uint32_t)(kk >> 7), bl = (uint32_t)(ll >> 7);
-        if (want) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                __builtin_amdgcn_global_load_lds(boff(bwt, bk, 4 * q), LDS_PTR(&W->img[q][0]), 16, 0, 0);
-        }
-        if (needl) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                __builtin_amdgcn_global_load_lds(boff(bwt, bl, 4 * q), LDS_PTR(&W->img[4 + q][0]), 16, 0, 0);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int lane = vlane();
-        vk = Bucket{W->img[0][lane], W->img[1][lane], W->img[2][lane], W->img[3][lane]};
-        const int o = needl ? 4 : 0;  // read the l planes only where they were fetched
-        vl = Bucket{W->img[o][lane], W->img[o + 1][lane], W->img[o + 2][lane], W->img[o + 3][lane]};
-    } else {
-        uint4(*img)[4] = reinterpret_cast<uint4(*)[4]>(&W->img[0][0]);  // [k 64 | l 64][4 chunks]
-        const uint32_t bk = want ? (uint32_t)(kk >> 7) : NO_BUCKET;
-        const uint32_t bl = needl ? (uint32_t)(ll >> 7) : NO_BUCKET;
-        const int lane = vlane();
-        const uint32_t chunk = (uint32_t)(lane & 3) * 4;
-        // all 8 source lookups first (one LDS wait), then the 8 DMAs
-        uint32_t sk[4], sl[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int src = (16 * r + (lane >> 2)) << 2;  // ds_bpermute byte address
-            sk[r] = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)bk);
-            sl[r] = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)bl);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (sk[r] != NO_BUCKET) __builtin_amdgcn_global_load_lds(boff(bwt, sk[r], chunk), LDS_PTR(&img[16 * r][0]), 16, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (sl[r] != NO_BUCKET)
-                __builtin_amdgcn_global_load_lds(boff(bwt, sl[r], chunk), LDS_PTR(&img[64 + 16 * r][0]), 16, 0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        vk = Bucket{img[lane][0], img[lane][1], img[lane][2], img[lane][3]};
-        const uint4* src = needl ? &img[64 + lane][0] : &img[lane][0];
-        vl = Bucket{src[0], src[1], src[2], src[3]};
-    }
-}
-
-// One bwt_extend in one direction, returning only the child for base c,
-// from the two Occ buckets of k = a-1 and l = k+s.
-//   a: coordinate searched through the BWT (x[1] forward, x[0] backward)
-//   b: the other coordinate, s: interval size
-//   -> na = L2[c] + 1 + Occ(c, a-1), ns = Occ(c, a-1+s) - Occ(c, a-1),
-//      nb = b + [$ in interval] + sum_{c' > c} (Occ(c', a-1+s) - Occ(c', a-1))
-// (software/bwt.c:416-429; the four-way cumulative in :425-428 restricted
-// to the child actually taken).
-__device__ __forceinline__ void extend_counts(const SeedParams& P, uint64_t a, uint64_t b, uint64_t s, int c,
-                                              uint64_t kk, uint64_t ll, const Bucket& vk, const Bucket& vl,
-                                              uint64_t& na, uint64_t& nb, uint64_t& ns) {
-    uint32_t Ck, Gk, Tk, Cl, Gl, Tl;
-    const uint32_t pk = (uint32_t)(kk & 127), pl = (uint32_t)(ll & 127);
-    count_cgt(vk, pk, Ck, Gk, Tk);
-    count_cgt(vl, pl, Cl, Gl, Tl);
-    const uint32_t Ak = pk + 1 - Ck - Gk - Tk, Al = pl + 1 - Cl - Gl - Tl;
-    const uint64_t tk0 = cnt64(vk.c01, 0) + Ak, tk1 = cnt64(vk.c01, 1) + Ck;
-    const uint64_t tk2 = cnt64(vk.c23, 0) + Gk, tk3 = cnt64(vk.c23, 1) + Tk;
-    const uint64_t tl0 = cnt64(vl.c01, 0) + Al, tl1 = cnt64(vl.c01, 1) + Cl;
-    const uint64_t tl2 = cnt64(vl.c23, 0) + Gl, tl3 = cnt64(vl.c23, 1) + Tl;
-    const uint64_t d0 = tl0 - tk0, d1 = tl1 - tk1, d2 = tl2 - tk2, d3 = tl3 - tk3;
-    const uint64_t L2c = sel4(c, P.L2[0], P.L2[1], P.L2[2], P.L2[3]);
-    na = L2c + 1 + sel4(c, tk0, tk1, tk2, tk3);
-    ns = sel4(c, d0, d1, d2, d3);
-    const uint64_t gt = (c < 1 ? d1 : 0) + (c < 2 ? d2 : 0) + (c < 3 ? d3 : 0);
-    nb = b + (uint64_t)(a <= P.primary && a + s - 1 >= P.primary) + gt;
-}
 
 // ---- Occ64: the index re-laid for the GPU as one 32-B bucket per 64 BWT
 // symbols (same 0.5 B/symbol as the reference's 64 B per 128).  Words 0-2:
@@ -312,9 +162,14 @@ __device__ __forceinline__ void rank192(const Bucket32& v, uint64_t kk, uint64_t
     }
 }
 
-// bwt_extend for the child c only (as extend_counts) on Occ64 buckets (or
-// Occ192 lines)
-template <bool L192 = false>
+// One bwt_extend in one direction on Occ64 buckets (or Occ192 lines), returning only the child for
+// base c, from the buckets of k = a-1 and l = k+s (kk, ll: the same rows without the $ row):
+//   a: coordinate searched through the BWT (x[1] forward, x[0] backward), b: the other, s: the size
+//   -> na = L2[c] + 1 + Occ(c, k), ns = Occ(c, l) - Occ(c, k),
+//      nb = b + [$ in interval] + sum_{c' > c} (Occ(c', l) - Occ(c', k))
+// (software/bwt.c:416-429; the four-way cumulative in :425-428 restricted to the child taken).
+// BSEL: the selects by c as bit tests (sel4b) and the sum over c' > c as suffix sums
+template <bool L192 = false, bool BSEL = false>
 __device__ __forceinline__ void extend_counts64(const SeedParams& P, uint64_t a, uint64_t b, uint64_t s, int c,
                                                 uint64_t kk, uint64_t ll, const Bucket32& vk, const Bucket32& vl,
                                                 uint64_t& na, uint64_t& nb, uint64_t& ns) {
@@ -331,6 +186,14 @@ __device__ __forceinline__ void extend_counts64(const SeedParams& P, uint64_t a,
     }
     const uint64_t tk0 = kk + 1 - tk1 - tk2 - tk3, tl0 = ll + 1 - tl1 - tl2 - tl3;
     const uint64_t d0 = tl0 - tk0, d1 = tl1 - tk1, d2 = tl2 - tk2, d3 = tl3 - tk3;
+    if constexpr (BSEL) {  // the selects by c's two bits; the suffix sums once, then one select
+        const uint64_t L2c = sel4b(c, P.L2[0], P.L2[1], P.L2[2], P.L2[3]);
+        na = L2c + 1 + sel4b(c, tk0, tk1, tk2, tk3);
+        ns = sel4b(c, d0, d1, d2, d3);
+        const uint64_t g2 = d2 + d3, g1 = d1 + g2;
+        nb = b + (uint64_t)(a <= P.primary && a + s - 1 >= P.primary) + sel4b(c, g1, g2, d3, 0);
+        return;
+    }
     const uint64_t L2c = sel4(c, P.L2[0], P.L2[1], P.L2[2], P.L2[3]);
     na = L2c + 1 + sel4(c, tk0, tk1, tk2, tk3);
     ns = sel4(c, d0, d1, d2, d3);
@@ -338,13 +201,6 @@ __device__ __forceinline__ void extend_counts64(const SeedParams& P, uint64_t a,
     nb = b + (uint64_t)(a <= P.primary && a + s - 1 >= P.primary) + gt;
 }
 
-// Fetch the Occ64 buckets of k and l (issue: DMAs, tags; read: after the
-// wave's vmcnt wait).  Each lane keeps the two buckets it
-// fetched last in two LDS slots (planes [2*slot + chunk][lane]) with their
-// indices in t0 / t1: consecutive extends of one lane often need the same
-// bucket again (nested intervals of one backward step: 30 % of the buckets
-// on the bench workload), and those are not fetched again.  Every lane DMAs
-// its own buckets, one 16-B chunk per instruction (at most 4 instructions).
 // the two 16-B chunks of 64-symbol block b: Occ64 bucket b, or Occ192 line b / 3
 template <bool L192>
 __device__ __forceinline__ void block_chunks(const uint32_t* __restrict__ occ, uint32_t b, const uint32_t*& c0,
@@ -357,90 +213,6 @@ __device__ __forceinline__ void block_chunks(const uint32_t* __restrict__ occ, u
         c0 = boff(occ, b >> 1, (b & 1) * 8);
         c1 = boff(occ, b >> 1, (b & 1) * 8 + 4);
     }
-}
-
-template <class WL, bool L192 = false>
-__device__ __forceinline__ void fetch_occ64_issue(const uint32_t* __restrict__ occ, WL* W, uint64_t kk, uint64_t ll,
-                                                  uint32_t& t0, uint32_t& t1, int& ks, int& ls) {
-    const uint32_t bk = (uint32_t)(kk >> 6), bl = (uint32_t)(ll >> 6);
-    const bool needl = bk != bl;
-    ks = bk == t0 ? 0 : (bk == t1 ? 1 : -1);
-    ls = !needl ? ks : (bl == t0 ? 0 : (bl == t1 ? 1 : -1));
-    const bool kmiss = ks < 0, lmiss = needl && ls < 0;
-    if (kmiss) ks = (needl && ls == 0) ? 1 : 0;  // keep the slot l hits
-    if (!needl) ls = ks;
-    else if (lmiss) ls = ks ^ 1;
-    const bool f0 = (kmiss && ks == 0) || (lmiss && ls == 0);
-    const bool f1 = (kmiss && ks == 1) || (lmiss && ls == 1);
-    const uint32_t b0 = (kmiss && ks == 0) ? bk : bl, b1 = (kmiss && ks == 1) ? bk : bl;
-    if (f0) {
-        const uint32_t *a0, *a1;
-        block_chunks<L192>(occ, b0, a0, a1);
-        __builtin_amdgcn_global_load_lds(a0, LDS_PTR(&W->img[0][0]), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds(a1, LDS_PTR(&W->img[1][0]), 16, 0, 0);
-        t0 = b0;
-    }
-    if (f1) {
-        const uint32_t *a0, *a1;
-        block_chunks<L192>(occ, b1, a0, a1);
-        __builtin_amdgcn_global_load_lds(a0, LDS_PTR(&W->img[2][0]), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds(a1, LDS_PTR(&W->img[3][0]), 16, 0, 0);
-        t1 = b1;
-    }
-}
-
-// The same slot policy with the two slots in registers (VSLOT): the missing
-// buckets are loaded straight into s0 / s1 (the lanes that hit keep theirs)
-// NT: the bucket loads non-temporal (streamed through L2 without displacing
-// the lanes' list-arena and output lines)
-typedef uint32_t nt_v4u __attribute__((ext_vector_type(4)));
-template <bool L192 = false, bool NT = false>
-__device__ __forceinline__ uint4 ld_bucket16(const uint32_t* a) {
-    if constexpr (NT) {
-        const nt_v4u v = __builtin_nontemporal_load(reinterpret_cast<const nt_v4u*>(a));
-        return make_uint4(v.x, v.y, v.z, v.w);
-    }
-    return *reinterpret_cast<const uint4*>(a);
-}
-template <bool L192 = false, bool NT = false>
-__device__ __forceinline__ void fetch_occ64_issue_regs(const uint32_t* __restrict__ occ, uint64_t kk, uint64_t ll,
-                                                       uint32_t& t0, uint32_t& t1, int& ks, int& ls, uint4& s0a,
-                                                       uint4& s0b, uint4& s1a, uint4& s1b) {
-    const uint32_t bk = (uint32_t)(kk >> 6), bl = (uint32_t)(ll >> 6);
-    const bool needl = bk != bl;
-    ks = bk == t0 ? 0 : (bk == t1 ? 1 : -1);
-    ls = !needl ? ks : (bl == t0 ? 0 : (bl == t1 ? 1 : -1));
-    const bool kmiss = ks < 0, lmiss = needl && ls < 0;
-    if (kmiss) ks = (needl && ls == 0) ? 1 : 0;  // keep the slot l hits
-    if (!needl) ls = ks;
-    else if (lmiss) ls = ks ^ 1;
-    const bool f0 = (kmiss && ks == 0) || (lmiss && ls == 0);
-    const bool f1 = (kmiss && ks == 1) || (lmiss && ls == 1);
-    const uint32_t b0 = (kmiss && ks == 0) ? bk : bl, b1 = (kmiss && ks == 1) ? bk : bl;
-    if (f0) {
-        const uint32_t *a0, *a1;
-        block_chunks<L192>(occ, b0, a0, a1);
-        s0a = ld_bucket16<L192, NT>(a0);
-        s0b = ld_bucket16<L192, NT>(a1);
-        t0 = b0;
-    }
-    if (f1) {
-        const uint32_t *a0, *a1;
-        block_chunks<L192>(occ, b1, a0, a1);
-        s1a = ld_bucket16<L192, NT>(a0);
-        s1b = ld_bucket16<L192, NT>(a1);
-        t1 = b1;
-    }
-}
-
-// after the wait: the lane's k and l buckets from its slots
-template <class WL>
-__device__ __forceinline__ void fetch_occ64_read(WL* W, int ks, int ls, Bucket32& vk, Bucket32& vl) {
-    const int lane = vlane();
-    ks = ks < 0 ? 0 : ks;  // lanes without a request read a slot and ignore it
-    ls = ls < 0 ? 0 : ls;
-    vk = Bucket32{W->img[2 * ks][lane], W->img[2 * ks + 1][lane]};
-    vl = Bucket32{W->img[2 * ls][lane], W->img[2 * ls + 1][lane]};
 }
 
 // offsets of work item `it` (read_ids maps overflow-pass items to reads)
@@ -459,12 +231,6 @@ __device__ __forceinline__ void next_offsets(const SeedParams& P, int it, uint32
 __device__ __forceinline__ uint64_t rtstamp() {
     uint64_t t;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-
-__device__ __forceinline__ uint64_t stamp() {
-    uint64_t t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
     return t;
 }
 
@@ -550,6 +316,15 @@ __device__ __forceinline__ uint32_t mbcnt64(uint64_t m) {
 
 __device__ __forceinline__ int hibit64(uint64_t m) { return 63 - __builtin_clzll(m); }
 
+// A register that no instruction sets: the value is whatever the lane's register held.  Defined
+// (an empty asm "writes" it), unlike an uninitialised variable, and arbitrary: only for a variable
+// that every lane which goes on to use it assigns first (seed_wp_kernel's DIET 16)
+__device__ __forceinline__ uint32_t idle_u32() {
+    uint32_t v;
+    asm volatile("" : "=v"(v));
+    return v;
+}
+
 // LDS accesses of one wave execute in order; this keeps the compiler from
 // moving them across the point where another lane's write must be seen
 __device__ __forceinline__ void wave_lds_fence() {
@@ -576,8 +351,16 @@ __device__ __forceinline__ void wave_lds_fence() {
 // query-window / offsets DMA and the claim issued after the entry has landed (else before it: the
 // compiler's wait for the entry covers them), 8 the claim as one hand-issued atomic per wave waited
 // for by the iteration's vmcnt(0) (else the compiler's atomicAdd at the top, which waits for it)
+// DIET (A/B of the instructions one wave-iteration issues, DESIGN.md §5 "The iteration's instruction
+// diet"; every arm is in unless its bit is set in OPT, so the default stays OPT = 15): 16 the uniform
+// section's temporaries start undefined in lanes without a task (out: zeroed, a v_mov each, every
+// iteration, for values nothing reads), 32 no `out` flag (a lane is at P_FWD_RES at the end of a pass
+// exactly when P_FWD has just asked for the extend), 64 the selects by base as two bit tests (sel4b;
+// out: sel4's compare chain, which compiles to a branch tree), 128 the query byte by one bit test and
+// a 64-bit shift (out: qsel's compare chain, a branch tree again)
 template <int OWN, int NL, int PRIO, int WPE = 3, bool PAIR = false, bool KT = false, bool DPOS = false, int OPT = 15>
 __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
+    constexpr int DIET = ~OPT;  // bits 16-128 of OPT take an arm of the diet out
     static_assert(!(DPOS && PAIR), "DPOS keeps the owner lane where PAIR keeps prev_n");
     constexpr uint32_t PR = PAIR ? 2u : 1u;  // entries per worker lane
     const int K = KT && P.kt ? P.kt_k : 0;
@@ -591,13 +374,8 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
     // an owner's arena: [0, cap) the forward list beyond the ring, [cap, 2 cap) curr / prev beyond NL;
     // one per owner (OWN a wave, numbered from wown), not per lane: the batch's scratch is 64 / OWN
     // times smaller (smem_gpu.cpp seed_arenas)
-#ifdef SMEM_WP_ARENA_PER_LANE  // (A/B: round 5's one arena per lane)
-    const uint64_t wown = wave_g;
-    PIntv* __restrict__ bp = reinterpret_cast<PIntv*>(P.scratch + (wown + (uint64_t)me) * 2ull * cap);
-#else
     const uint64_t wown = (wave_g >> 6) * (uint64_t)OWN;
     PIntv* __restrict__ bp = reinterpret_cast<PIntv*>(P.scratch + (wown + (uint64_t)(me < OWN ? me : 0)) * 2ull * cap);
-#endif
 
     int phase = me < OWN ? P_FETCH : P_EXIT;  // lanes >= OWN only execute extends
     int item = -1, len = 0;
@@ -701,6 +479,24 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         }                                                                                                                     \
     }
 
+// the start value of the uniform section's per-task temporaries (see there)
+#define WP_IDLE32() ((DIET & 16) ? idle_u32() : 0u)
+#define WP_IDLE128() ((DIET & 16) ? make_uint4(idle_u32(), idle_u32(), idle_u32(), idle_u32()) : make_uint4(0, 0, 0, 0))
+// the lane yields this pass (DIET 32: nothing to note, see fwdreq)
+#define WP_OUT()                         \
+    {                                    \
+        if constexpr (!(DIET & 32)) out = true; \
+    }
+// one forward push (software/bwt.c:797, 802): the ring's oldest entry moves to the arena first
+#define WP_PUSH()                                                                                                \
+    {                                                                                                            \
+        const uint4 fe = pack_p(ik0, ik1, ik2, ikend);                                                           \
+        if (fwd_n >= (uint32_t)NL) *reinterpret_cast<uint4*>(bp + cap - 1 - (fwd_n - NL)) = L->e[lr][me];        \
+        L->e[lr][me] = fe;                                                                                       \
+        lr = lr + 1 == (uint32_t)NL ? 0u : lr + 1;                                                               \
+        ++fwd_n;                                                                                                 \
+    }
+
     for (;;) {
         if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(2);
         if (phase != P_EXIT) {
@@ -730,7 +526,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         }
         // ---- owners: advance the state machine one pass (seed_kernel's
         // blocks, without the per-entry backward block) ----
-        bool out = false;
+        [[maybe_unused]] bool out = false;
         if (phase != P_EXIT) {
             if (phase == P_SMEM_END) {
                 if (!middle) {  // software/bwamem.c:261-272
@@ -756,7 +552,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             }
             if (phase == P_FETCH) {
                 if (nlen < 0) {
-                    out = true;
+                    WP_OUT();
                 } else if (nitem >= P.n_items) {
                     phase = P_EXIT;
                 } else {
@@ -770,7 +566,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                     start = 0;
                     if (len < P.min_seed_len) {  // mem_chain's guard (software/bwamem.c:600)
                         *reinterpret_cast<uint4*>(P.sizes + 2 * (uint64_t)rid) = make_uint4(0, 0, 0, 0);
-                        out = true;
+                        WP_OUT();
                     } else {
                         phase = P_NEXT2;
                     }
@@ -782,13 +578,13 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                     for (;;) {
                         if (start >= len) break;
                         if (QBLK(start) != qb) { wait_q = true; break; }
-                        if (qsel(o0, start, qv) <= 3) break;
+                        if (qsel<(DIET & 128) != 0>(o0, start, qv) <= 3) break;
                         ++start;
                     }
                 }
                 if (wait_q) {
                     qwant = QBLK(start);
-                    out = true;
+                    WP_OUT();
                 } else if (start >= len || start < 0) {
                     if (raw_n & 1) {  // an odd count: the last record goes out alone
                         uint4* ln_ = reinterpret_cast<uint4*>(P.out_intv + (uint64_t)item * P.slot_intv + (raw_n - 1));
@@ -809,20 +605,24 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             if (phase == P_SMEM_BEGIN) {  // software/bwt.c:782-789
                 if (QBLK(x) != qb) {
                     qwant = QBLK(x);
-                    out = true;
+                    WP_OUT();
                 } else {
                     mem_n = 0;
-                    const int qx = qsel(o0, x, qv);
+                    const int qx = qsel<(DIET & 128) != 0>(o0, x, qv);
                     if (qx > 3) {
                         ret = x + 1;
                         phase = P_SMEM_END;
                     } else {
                         if (min_intv < 1) min_intv = 1;
-                        const uint64_t lq = sel4(qx, P.L2[0], P.L2[1], P.L2[2], P.L2[3]);
-                        const uint64_t lq1 = sel4(qx, P.L2[1], P.L2[2], P.L2[3], P.L2[4]);
+                        const uint64_t lq = (DIET & 64) ? sel4b(qx, P.L2[0], P.L2[1], P.L2[2], P.L2[3])
+                                                         : sel4(qx, P.L2[0], P.L2[1], P.L2[2], P.L2[3]);
+                        const uint64_t lq1 = (DIET & 64) ? sel4b(qx, P.L2[1], P.L2[2], P.L2[3], P.L2[4])
+                                                          : sel4(qx, P.L2[1], P.L2[2], P.L2[3], P.L2[4]);
+                        const uint64_t lc = (DIET & 64) ? sel4b(qx, P.L2[3], P.L2[2], P.L2[1], P.L2[0])
+                                                         : sel4(qx, P.L2[3], P.L2[2], P.L2[1], P.L2[0]);
                         ik0 = lq + 1;
                         ik2 = lq1 - lq;
-                        ik1 = sel4(qx, P.L2[3], P.L2[2], P.L2[1], P.L2[0]) + 1;
+                        ik1 = lc + 1;
                         ikend = (uint32_t)(x + 1);
                         if constexpr (KT) kc = (uint32_t)qx;
                         fwd_n = 0;
@@ -849,11 +649,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             if (phase == P_FWD_RES) {  // software/bwt.c:795-799; na = x[1], nb = x[0]
                 bool stop = false;
                 if (ns != ik2) {
-                    const uint4 fe = pack_p(ik0, ik1, ik2, ikend);
-                    if (fwd_n >= (uint32_t)NL) *reinterpret_cast<uint4*>(bp + cap - 1 - (fwd_n - NL)) = L->e[lr][me];
-                    L->e[lr][me] = fe;
-                    lr = lr + 1 == (uint32_t)NL ? 0u : lr + 1;
-                    ++fwd_n;
+                    WP_PUSH()
                     stop = ns < (uint64_t)min_intv;
                 }
                 if (stop) {
@@ -873,25 +669,21 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                 if (i < len) {
                     if (QBLK(i) != qb) {
                         qwant = QBLK(i);
-                        out = true;
+                        WP_OUT();
                         push = false;
                     } else {
-                        const int qi = qsel(o0, i, qv);
+                        const int qi = qsel<(DIET & 128) != 0>(o0, i, qv);
                         if (qi < 4) {
                             cur_c = 3 - qi;
                             if (i + 1 < len) qwant = QBLK(i + 1);
                             phase = P_FWD_RES;  // -> extend (forward), on this lane
-                            out = true;
+                            WP_OUT();
                             push = false;
                         }
                     }
                 }
                 if (push) {  // ambiguous base, or end of query: push ik and stop
-                    const uint4 fe = pack_p(ik0, ik1, ik2, ikend);
-                    if (fwd_n >= (uint32_t)NL) *reinterpret_cast<uint4*>(bp + cap - 1 - (fwd_n - NL)) = L->e[lr][me];
-                    L->e[lr][me] = fe;
-                    lr = lr + 1 == (uint32_t)NL ? 0u : lr + 1;
-                    ++fwd_n;
+                    WP_PUSH()
                     phase = P_FWD_DONE;
                 }
             }
@@ -911,9 +703,9 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             if (phase == P_BWD_STEP) {  // software/bwt.c:810-812
                 if (i >= 0 && QBLK(i) != qb) {
                     qwant = QBLK(i);
-                    out = true;
+                    WP_OUT();
                 } else {
-                    cur_c = i < 0 ? -1 : qsel(o0, i, qv);
+                    cur_c = i < 0 ? -1 : qsel<(DIET & 128) != 0>(o0, i, qv);
                     if (cur_c > 3) cur_c = -1;
                     if (cur_c >= 0) {
                         j = 0;
@@ -932,7 +724,8 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         }
         // ---- uniform section ----
         if (!__any(phase != P_EXIT)) break;
-        const bool fwdreq = out && phase == P_FWD_RES;
+        // (a lane is at P_FWD_RES here only when P_FWD has just set it: the P_FWD_RES block always leaves it)
+        const bool fwdreq = ((DIET & 32) || out) && phase == P_FWD_RES;
         const uint32_t rem = phase == P_BWD_WAIT ? prev_n - j : 0u;
         const uint32_t slots = (rem + PR - 1) / PR;  // worker lanes the step still needs
         if (!DPOS && rem) {  // what a worker needs of this owner's step
@@ -971,9 +764,20 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             marks = __ballot(L->tabS[me] != 0xFFu);
         }
         const bool worker = freel && rank < ntask;
-        uint32_t s = 0, o = 0, jj = 0, lro = 0;
+        // What only a worker sets and only a worker's results use.  DIET 16 leaves the other lanes'
+        // copies ARBITRARY (idle_u32), not zero, so this invariant holds and must keep holding:
+        //  * s, o, jj, lro, w0, w1, ent are assigned under `worker` below and read only under `worker`
+        //    (surv, keep, rank == s, tabP[s], RES[pp], the stores into the owner's list) or under `far`,
+        //    which only a worker sets -- obp, formed from `o` outside the branch, is dereferenced only
+        //    there; a forward lane (fwdreq) takes ra / rb / rs / rc from its own state, never from ent / w0,
+        //    and the KT path reads w1.w only where !fwdreq, i.e. on a worker;
+        //  * k0, k1, l0, l1 are loaded under `task` and read under `task` (l0 / l1 only where bl != bk);
+        //  * what comes out of arbitrary inputs in a lane without a task (kk, ll, bk, bl) reaches no
+        //    address: every load and store below is under `task`, `far`, `keep` or `take`.
+        // A new use of any of them outside those conditions reads garbage silently.
+        uint32_t s = WP_IDLE32(), o = WP_IDLE32(), jj = WP_IDLE32(), lro = WP_IDLE32();
         bool has2 = false;
-        uint4 w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0}, ent = {0, 0, 0, 0}, ent2 = {0, 0, 0, 0};
+        uint4 w0 = WP_IDLE128(), w1 = WP_IDLE128(), ent = WP_IDLE128(), ent2 = {0, 0, 0, 0};
         bool far = false, far2 = false;  // the entry (PAIR: the second) is in the owner's arena
         if (worker) {
             s = (uint32_t)hibit64(marks & ((2ull << rank) - 1ull));  // the segment holding task `rank`
@@ -1045,7 +849,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             asm volatile("" ::"v"(bk), "v"(bl) : "memory");
             WP_ISSUE();
         }
-        uint4 k0 = {0, 0, 0, 0}, k1 = {0, 0, 0, 0}, l0 = {0, 0, 0, 0}, l1 = {0, 0, 0, 0};
+        uint4 k0 = WP_IDLE128(), k1 = WP_IDLE128(), l0 = WP_IDLE128(), l1 = WP_IDLE128();
         // KT: a result of at most K bases from the table (forward: q[x, i]; backward: q[i, end))
         bool ktp = false;
         if constexpr (KT) {
@@ -1109,7 +913,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         } else if (task) {
             const Bucket32 wk{k0, k1};
             const Bucket32 wl = bl != bk ? Bucket32{l0, l1} : wk;
-            extend_counts64<false>(P, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
+            extend_counts64<false, (DIET & 64) != 0>(P, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
         }
         uint64_t na2 = 0, nb2 = 0, ns2 = 0;
         if constexpr (PAIR) {
@@ -1176,6 +980,10 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         wave_lds_fence();  // this iteration's LDS reads before the next one's writes
     }
 #undef WP_EMIT
+#undef WP_PUSH
+#undef WP_OUT
+#undef WP_IDLE32
+#undef WP_IDLE128
 #undef WSLOT
 #undef QBLK
     if (P.tspan && me == 0) atomicMax(reinterpret_cast<unsigned long long*>(P.tspan) + 1, (unsigned long long)rtstamp());
@@ -1261,14 +1069,14 @@ __global__ void ovf_slot_kernel(const int32_t* __restrict__ items, int n_ovf, in
 // ------------------------------------------------------------ host launchers
 // The product build instantiates the default kernel (seed_wp_kernel variant 49;
 // 0 names it too) and its k-mer table twin (54).  The other seed_wp_kernel
-// shapes and OPT-bit twins measured in round 5 (40-62 other than 49 / 54;
+// shapes and OPT-bit twins (40-67 other than 49 / 54;
 // DESIGN.md §5) are compiled only with SMEM_AB_VARIANTS (make AB=1): the
 // library ships no kernel whose numbers are already recorded.  (Rounds 1-4's
 // one-lane-per-read seed_kernel, variants 2-31, wrote the raw log format of
 // its time and left with it; its numbers are in DESIGN.md §5.)
 extern "C" int smem_seed_variant_built(int variant) {
 #ifdef SMEM_AB_VARIANTS
-    return variant == 0 || (variant >= 40 && variant <= 62);
+    return variant == 0 || (variant >= 40 && variant <= 67);
 #else
     return variant == 0 || variant == 49 || variant == 54;
 #endif
@@ -1309,6 +1117,14 @@ extern "C" hipError_t smem_launch_seed(const smem::SeedParams* P, int grid, int 
         case 60: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 11>), dim3(grid), dim3(block), 0, st, *P); break;
         case 61: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 14>), dim3(grid), dim3(block), 0, st, *P); break;
         case 62: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 7>), dim3(grid), dim3(block), 0, st, *P); break;
+        // 63-67: 49 with the instruction diet taken apart (OPT bits 16-128 take an arm out): 63 the idle
+        // lanes' temporaries zeroed, 64 the `out` flag, 65 the selects by base as compare chains, 66 the
+        // query byte by a compare chain, 67 none of the four (the kernel before the diet)
+        case 63: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 31>), dim3(grid), dim3(block), 0, st, *P); break;
+        case 64: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 47>), dim3(grid), dim3(block), 0, st, *P); break;
+        case 65: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 79>), dim3(grid), dim3(block), 0, st, *P); break;
+        case 66: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 143>), dim3(grid), dim3(block), 0, st, *P); break;
+        case 67: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 255>), dim3(grid), dim3(block), 0, st, *P); break;
 #endif
         // 54: the default's shape with the k-mer table (KT; smem_gpu_set_kmer_table, no table: plain)
         case 54: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
