@@ -264,6 +264,8 @@ int  smem_gpu_memory(smem_gpu_t *gpu, uint64_t *index_bytes, uint64_t *batch_byt
  * returned. */
 typedef int (*smem_chunk_fn)(void *ctx, int64_t chunk, int64_t first_read, int n_reads, const smem_batch_t *b);
 #define SMEM_STREAM_PAIRS   1   /* interleaved mates: chunks keep pairs whole */
+/* (a call with a read longer than SMEM_PINTV_MAX_LEN = 8191 bp is refused with SMEM_E_ARG before any
+ * chunk runs; the test suite covers packed reads of 8191 bp, and 8192 bp for the refusal) */
 #define SMEM_STREAM_PACKED  2   /* results as 16-B smem_pintv_t (smem_batch_results_packed): half the D2H */
 #define SMEM_STREAM_RELEASE 4   /* do not keep the workers' batches (pinned buffers) for the next call */
 typedef struct {
@@ -279,6 +281,12 @@ int  smem_gpu_seed_stream(smem_gpu_t *gpu, int64_t n_reads, const uint8_t *codes
                           void *ctx, smem_stream_stats_t *stats);
 
 /* ------------------------------------------------------- batch (explicit) */
+/* max_len: the longest read the batch will hold, 1 .. 2^24 (more is
+ * SMEM_E_ARG).  It sets the per-read output capacity (max_len / 2 + 32
+ * intervals; a read with more goes through the overflow pass) and the list
+ * arenas (max_len + 2 entries).  The test suite covers reads of 0 bp to
+ * 70,698 bp through seeding, smem_batch_sa and smem_batch_chain
+ * (tests/test_gpu_long_reads.py); nothing longer has been run. */
 int  smem_batch_create(smem_gpu_t *gpu, int max_reads, uint64_t max_bases, int max_len, smem_batch_t **b);
 void smem_batch_destroy(smem_batch_t *b);
 /* stage reads: per-read pointers (bseq1_t style) or one concatenated array

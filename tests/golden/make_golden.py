@@ -33,6 +33,11 @@ reference code itself:
     python tests/golden/make_golden.py --kswa-only     # (re)make only the ksw_align2 sets
     python tests/golden/make_golden.py --aln-only      # (re)make the region fixtures (*.smrg.gz, r3 / r4 and theirs)
     python tests/golden/make_golden.py --aln-options-only  # (re)make only r3 / r4 and their fixtures
+    python tests/golden/make_golden.py --long-only     # (re)make only long/ (on the committed g1 .bwt / .sa)
+  long/r5.smrd.gz     16 reads of 321 bp to 70 kbp on g1 (tests/long_reads.py class_reads)
+  long/g1_r5_default.smgo.gz, .smsa.gz, _std_f<0|1>.smch.gz
+                      the reference's lists, bwt_sa positions (max_occ 10000) and chains of them
+                      under the default options; long/manifest.json
   r3.smrd.gz, r4.smrd.gz  reads of g1 / g2 with indels, junk stretches, mismatched ends and unrelated
                       tails (tests/aln_reads.py), their filtered chains <g>_<r>_<std|k10|w1|w7>_std_f1.smch.gz
   <g>_<r>_<set>.smrg.gz  the reference's regions of those reads under each option set of
@@ -626,8 +631,70 @@ def make_aln_options():
         shutil.rmtree(tmp)
 
 
+# reads of 321 bp to 70 kbp (tests/long_reads.py class_reads): seeding, SA
+# lookup and chains of the reference under the default options, in long/
+LONG_SEED = 401
+LONG_OPT = dict(min_seed_len=19, split_factor=1.5, split_width=10, start_width=1)
+
+
+def make_long():
+    from tests import golden_data, long_reads
+    if not oracle.ref_available():
+        oracle.build(ref=True)
+    out_dir = os.path.join(HERE, "long")
+    os.makedirs(out_dir, exist_ok=True)
+    tmp = tempfile.mkdtemp()
+    try:
+        for name in ("g1.bwt", "g1.sa"):
+            with gzip.open(os.path.join(HERE, name + ".gz"), "rb") as fh, open(os.path.join(tmp, name), "wb") as o:
+                o.write(fh.read())
+        with gzip.open(os.path.join(HERE, "g1.fa.gz"), "rb") as fh:
+            G = golden_data.fasta_codes(fh.read())
+        named = long_reads.class_reads(G, LONG_SEED)
+        reads = long_reads.reads_of(named)
+        smrd = os.path.join(tmp, "r5.smrd")
+        synth.write_smrd(smrd, reads)
+        with open(smrd, "rb") as fh:
+            rd = fh.read()
+        gz_write(os.path.join(out_dir, "r5.smrd.gz"), rd)
+        out = os.path.join(tmp, "default.smgo")
+        oracle.ref_smem(os.path.join(tmp, "g1.bwt"), smrd, out, **LONG_OPT)
+        with open(out, "rb") as fh:
+            data = fh.read()
+        gz_write(os.path.join(out_dir, "g1_r5_default.smgo.gz"), data)
+        parsed = synth.read_smgo(data)
+        sa_out = os.path.join(tmp, "default.smsa")
+        oracle.ref_sa(os.path.join(tmp, "g1.bwt"), os.path.join(tmp, "g1.sa"), out, sa_out,
+                      min_seed_len=LONG_OPT["min_seed_len"], max_occ=MAX_OCC)
+        with open(sa_out, "rb") as fh:
+            sa_data = fh.read()
+        gz_write(os.path.join(out_dir, "g1_r5_default.smsa.gz"), sa_data)
+        case = dict(name="default", opt=LONG_OPT, n_reads=reads.n, sha256=hashlib.sha256(data).hexdigest(),
+                    n_intv=int(sum(a.shape[0] for r in parsed for a in r)), n_calls=int(sum(len(r) for r in parsed)),
+                    max_occ=MAX_OCC, sa_sha256=hashlib.sha256(sa_data).hexdigest(),
+                    n_occ=int(sum(p.size for p in synth.read_smsa(sa_data))), chains=[])
+        std = next(c for c in CHAIN_OPTS if c["name"] == "std")
+        for filt in (0, 1):
+            cd = ref_chain(tmp, smrd, case, std, filt)
+            fn = f"g1_r5_default_std_f{filt}.smch.gz"
+            gz_write(os.path.join(out_dir, fn), cd)
+            case["chains"].append(dict(std, file=fn, filter=filt, sha256=hashlib.sha256(cd).hexdigest()))
+        manifest = dict(genome="g1", seed=LONG_SEED,
+                        reads=dict(file="r5.smrd.gz", n_reads=reads.n, n_bases=int(reads.codes.size),
+                                   names=[n for n, _ in named], lens=[int(x) for x in reads.lens],
+                                   sha256=hashlib.sha256(rd).hexdigest()),
+                        cases=[case])
+        with open(os.path.join(out_dir, "manifest.json"), "w") as fh:
+            json.dump(manifest, fh, indent=1)
+        print(json.dumps(manifest, indent=1))
+    finally:
+        shutil.rmtree(tmp)
+
+
 if __name__ == "__main__":
-    if "--aln-only" in sys.argv:
+    if "--long-only" in sys.argv:
+        make_long()
+    elif "--aln-only" in sys.argv:
         make_aln()
     elif "--aln-options-only" in sys.argv:
         make_aln_options()

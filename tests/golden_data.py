@@ -135,6 +135,48 @@ def files(genome: str, d: str):
     return out
 
 
+# ---- reads of 321 bp to 70 kbp on g1 (tests/golden/long/) -----------------
+def long_manifest() -> dict:
+    with open(os.path.join(GOLDEN, "long", "manifest.json")) as fh:
+        return json.load(fh)
+
+
+def long_case() -> dict:
+    """the one seeding case of the long-read fixture (the default options)"""
+    return long_manifest()["cases"][0]
+
+
+def long_reads():
+    """the r5 reads as smemgpu.synth.Reads, and their names (tests/long_reads.py)"""
+    import tempfile
+    from smemgpu import synth
+    m = long_manifest()["reads"]
+    data = _gz(os.path.join("long", m["file"]))
+    assert hashlib.sha256(data).hexdigest() == m["sha256"], "fixture corrupted"
+    with tempfile.TemporaryDirectory() as d:
+        p = os.path.join(d, "r5.smrd")
+        with open(p, "wb") as fh:
+            fh.write(data)
+        return synth.read_smrd(p), m["names"]
+
+
+def long_smgo() -> bytes:
+    data = _gz(os.path.join("long", "g1_r5_default.smgo.gz"))
+    assert hashlib.sha256(data).hexdigest() == long_case()["sha256"], "fixture corrupted"
+    return data
+
+
+def long_smsa() -> bytes:
+    data = _gz(os.path.join("long", "g1_r5_default.smsa.gz"))
+    assert hashlib.sha256(data).hexdigest() == long_case()["sa_sha256"], "fixture corrupted"
+    return data
+
+
+def long_smch(filt: int) -> bytes:
+    ch = next(c for c in long_case()["chains"] if c["filter"] == filt)
+    return smch(dict(ch, file=os.path.join("long", ch["file"])))
+
+
 # ---- chains -> regions (mem_chain2aln) fixtures ----------------------------
 ALNREG_DT = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"),
                       ("truesc", "<i4"), ("sub", "<i4"), ("csub", "<i4"), ("sub_n", "<i4"), ("w", "<i4"),
