@@ -259,8 +259,14 @@ constexpr uint32_t CHAIN_HEAVY_MIN = 16, CHAIN_GIANT_MIN = 2048, CHAIN_HEAVY_LDS
 
 // the seeding kernel a handle starts with: seed_wp_kernel<24 owners per wave, 18 LDS
 // list entries, 4 blocks per CU> (variant 49; variant 2 is the
-// lane-per-read seed_kernel of rounds 1-4)
+// lane-per-read seed_kernel of rounds 1-4).  A handle left on this default runs
+// the shape's instantiation with the short entries virtual (68) while it holds a
+// k-mer table with a usable depth (seed_run_variant); 49 asked for by number is
+// the plain kernel, whatever tables the handle holds
 constexpr int kSeedDefault = 49;
+constexpr int kSeedSkip = 68;
+// the k-mer table a handle builds for itself (SMEM_GPU_KMER_K: another depth, 0: none)
+constexpr int kKmerDefault = 12;
 // the persistent grid's lanes per CU when the caller sets none: 4 blocks of 256
 // fit the 4-block variants' LDS, but a grid of exactly 4 per CU leaves no VGPR
 // room for the finalize / compaction kernels of another batch (measured: the
@@ -268,7 +274,8 @@ constexpr int kSeedDefault = 49;
 static int seed_lanes_per_cu(int variant) {
     switch (variant) {
         case 44: case 45: case 46: case 49: case 50: case 51: case 52: case 53: case 54: case 56: case 57:
-        case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: return 960;
+        case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67:
+        case 68: case 69: case 70: return 960;
         default: return 768;
     }
 }
@@ -276,10 +283,10 @@ static int seed_lanes_per_cu(int variant) {
 // reads a wave of the seeding kernel owns at once (seed_wp_kernel<OWN, ...>; seed_kernel: one per lane)
 static int seed_owners_per_wave(int variant) {
     switch (variant) {
-        case 40: case 41: case 43: case 45: case 47: case 55: return 32;
+        case 40: case 41: case 43: case 45: case 47: case 55: case 69: return 32;
         case 42: case 44: case 48: case 49: case 51: case 52: case 54: case 56: case 57:
-        case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: return 24;
-        case 46: case 53: return 28;
+        case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: case 68: return 24;
+        case 46: case 53: case 70: return 28;
         case 50: return 20;
         default: return 64;
     }
@@ -298,11 +305,15 @@ struct smem_gpu {
     int lanes_per_cu = 0;  // 0: the seeding kernel's own (seed_lanes_per_cu)
     int intv_cap = 0;
     int variant = kSeedDefault;  // see smem_gpu_set_kernel_variant
+    bool plain49 = false;        // 49 was asked for by number: never run 68 in its place
     uint32_t* d_bwt = nullptr;      // reference layout (A/B variants 3, 4; freed after the Occ64 re-layout otherwise)
     uint32_t* d_occ64 = nullptr;    // Occ64 layout (default kernel)
     uint32_t* d_occ192 = nullptr;   // Occ192 layout (variant 10)
     uint4* d_kt = nullptr;          // k-mer bi-interval table (smem_gpu_set_kmer_table; variant 23)
     int kt_k = 0;
+    int kt_d = 0;                   // the table's facts (kmer_facts): see SeedParams::kt_d, kt_min
+    uint64_t kt_min[16] = {0};
+    double kt_build_s = 0.0;        // seconds the table's build and reduction took
     uint64_t* d_sa = nullptr;       // sampled SA (smem_gpu_load_sa), n_sa + 1 words
     uint8_t* d_pac = nullptr;       // 2-bit forward strand (smem_gpu_load_pac)
     // raw regions -> final regions: the host libm's log tables (fin_tables), made on first use;
@@ -742,7 +753,7 @@ static smem_gpu_t* gpu_handle(int device, uint64_t bwt_size, uint64_t primary, c
         // through smem_gpu_set_kernel_variant / their own setup)
         if (sv > 0 && smem_seed_variant_built(sv) && sv != 3 && sv != 4 && sv != 9 && sv != 10 && sv != 22 &&
             sv != 23 && sv != 25)
-            g->variant = sv;
+            g->variant = sv, g->plain49 = sv == kSeedDefault;
     }
     // the CU count before any async init starts (smem_gpu_grid_reads may read it at once)
     if (hipDeviceGetAttribute(&g->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) g->n_cu = 0;
@@ -752,8 +763,10 @@ static smem_gpu_t* gpu_handle(int device, uint64_t bwt_size, uint64_t primary, c
     return g;
 }
 
-// the index resident on g's device: upload, Occ64 re-layout (the device
-// pointers stay null on failure)
+static int kmer_table_build(smem_gpu_t* g, int k, const char* who);
+
+// the index resident on g's device: upload, Occ64 re-layout, the k-mer table
+// (the index pointers stay null on failure)
 static int gpu_open(smem_gpu_t* g, const uint32_t* bwt) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(SMEM_E_DEVICE, "smem_gpu_init: no HIP device");
@@ -803,6 +816,26 @@ static int gpu_open(smem_gpu_t* g, const uint32_t* bwt) {
     if (e == hipSuccess) e = smem_preload_ksw();
     if (e == hipSuccess) e = smem_preload_aln();
     if (e != hipSuccess) return fail(SMEM_E_DEVICE, "smem_gpu_init: code objects", e);
+    // the default kernel's k-mer table (the index is constant for the handle's life), built where the
+    // Occ64 layout above is: on the null stream, before any batch exists.  A table that cannot be
+    // ALLOCATED is not an error: the kernel then runs every call on the plain path.  Any other failure
+    // (a device error while building) fails the handle like the Occ64 layout's does
+    int kk = kKmerDefault;
+    // (the handle's own table is at most kKmerDefault deep: 13 would be 1.4 GB, 15 23 GB;
+    // smem_gpu_set_kmer_table takes a deeper one from a caller who means it)
+    if (const char* v = getenv("SMEM_GPU_KMER_K")) kk = std::max(0, std::min(kKmerDefault, atoi(v)));
+    // (no deeper than the index has strings for: 4^k <= its length)
+    while (kk > 1 && (1ull << (2 * kk)) > g->L2[4]) --kk;
+    if (kk > 0) {
+        const int rc = kmer_table_build(g, kk, "smem_gpu_init: k-mer table");
+        if (rc == SMEM_E_NOMEM) {
+            fprintf(stderr, "[smem_gpu] no memory for the k-mer table of depth %d: seeding runs the plain kernel\n", kk);
+            (void)hipGetLastError();
+            g_err[0] = 0;
+        } else if (rc != SMEM_OK) {
+            return rc;
+        }
+    }
     return SMEM_OK;
 }
 
@@ -835,7 +868,7 @@ int smem_gpu_set_lanes_per_cu(smem_gpu_t* g, int lanes_per_cu) {
 
 int smem_gpu_set_kernel_variant(smem_gpu_t* g, int variant) {
     g_err[0] = 0;
-    if (!g || !(variant == 0 || (variant >= 2 && variant <= 31) || (variant >= 40 && variant <= 67)))
+    if (!g || !(variant == 0 || (variant >= 2 && variant <= 31) || (variant >= 40 && variant <= 70)))
         return fail(SMEM_E_ARG, "smem_gpu_set_kernel_variant");
 
     if (!smem_seed_variant_built(variant))
@@ -859,10 +892,23 @@ int smem_gpu_set_kernel_variant(smem_gpu_t* g, int variant) {
         g->d_occ192 = p;
     }
     g->variant = variant == 0 ? kSeedDefault : variant;
+    g->plain49 = variant == kSeedDefault;
     return SMEM_OK;
 }
 
 int smem_gpu_get_kernel_variant(const smem_gpu_t* g) { return g ? g->variant : SMEM_E_ARG; }
+
+// the instantiation a launch runs: the default's shape with the short entries virtual where the
+// handle's table allows it (a depth below 2 skips nothing)
+static int seed_run_variant(const smem_gpu_t* g) {
+    return g->variant == kSeedDefault && !g->plain49 && g->d_kt && g->kt_d >= 2 ? kSeedSkip : g->variant;
+}
+
+int smem_gpu_seed_kernel(smem_gpu_t* g) {
+    if (!g) return SMEM_E_ARG;
+    gpu_wait(g);
+    return seed_run_variant(g);
+}
 
 int smem_gpu_grid_reads(const smem_gpu_t* g) {
     if (!g) return SMEM_E_ARG;
@@ -873,6 +919,63 @@ int smem_gpu_grid_reads(const smem_gpu_t* g) {
     return (int)((int64_t)n_cu * lpc / 64 * seed_owners_per_wave(g->variant));
 }
 
+// D of a table's per-level minimum sizes mn[1..k]: the largest level D < k such that no string of
+// D + 1 bases is absent (every level up to D + 1 is then complete: a level's minimum is at most the
+// one before it).  Up to D bases every extension of a present string is strictly smaller.
+int smem_kmer_depth(const uint64_t* mn, int k) {
+    int d = 0;
+    while (d + 1 <= k && d + 1 <= 15 && mn[d + 1] > 0) ++d;  // d: the deepest complete level
+    return d > 0 ? d - 1 : 0;
+}
+
+// the probe depth of a bwt_smem1 call: the largest level <= D whose smallest interval holds min_intv
+// (the kernel's choice, seed_wp_kernel SKIP; below 2 the call runs the plain path)
+int smem_kmer_call_depth(const uint64_t* mn, int D, int64_t min_intv) {
+    if (min_intv < 1) min_intv = 1;
+    int dp = 0;
+    for (int l = 1; l <= D && l <= 15; ++l)
+        if (mn[l] >= (uint64_t)min_intv) dp = l;
+    return dp;
+}
+
+// the table of 1..k bases and its facts on g's device (g->mu held, no batch running); k = 0 frees it
+static int kmer_table_build(smem_gpu_t* g, int k, const char* who) {
+    if (g->d_kt) {
+        HIP_TRY(hipDeviceSynchronize());  // no batch may still read it
+        (void)hipFree(g->d_kt);
+        g->d_kt = nullptr;
+        g->kt_k = g->kt_d = 0;
+        std::memset(g->kt_min, 0, sizeof(g->kt_min));
+    }
+    if (k == 0) return SMEM_OK;
+    const double t0 = now_s();
+    const uint64_t n = ((1ull << (2 * (k + 1))) - 4) / 3;  // levels 1..k
+    uint4* p = nullptr;
+    unsigned long long* d_mn = nullptr;
+    hipError_t e = hipMalloc(&p, n * sizeof(uint4));
+    if (e != hipSuccess) return fail(SMEM_E_NOMEM, who, e);
+    e = hipMalloc(&d_mn, 16 * sizeof(unsigned long long));
+    unsigned long long mn[16] = {0};
+    if (e == hipSuccess) e = smem_launch_kmer_table(g->d_occ64, g->primary, g->L2, k, p, nullptr);
+    if (e == hipSuccess) e = smem_launch_kmer_min(p, k, d_mn, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(mn, d_mn, sizeof(unsigned long long) * (size_t)(k + 1), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (d_mn) (void)hipFree(d_mn);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return fail(SMEM_E_DEVICE, who, e);
+    }
+    g->d_kt = p;
+    g->kt_k = k;
+    for (int l = 1; l <= k; ++l) g->kt_min[l] = mn[l];
+    g->kt_d = smem_kmer_depth(g->kt_min, k);
+    g->kt_build_s = now_s() - t0;
+    if (getenv("SMEM_GPU_TIMES"))
+        fprintf(stderr, "[smem_gpu] k-mer table: k %d, %.1f MB, D %d, minsz[D] %llu, built in %.3f s\n", k,
+                n * 16.0 / 1e6, g->kt_d, (unsigned long long)g->kt_min[g->kt_d], g->kt_build_s);
+    return SMEM_OK;
+}
+
 int smem_gpu_set_kmer_table(smem_gpu_t* g, int k) {
     g_err[0] = 0;
     if (!g || k < 0 || k > 15) return fail(SMEM_E_ARG, "smem_gpu_set_kmer_table: k must be 0..15");
@@ -880,25 +983,15 @@ int smem_gpu_set_kmer_table(smem_gpu_t* g, int k) {
     if (int r = gpu_check(g)) return r;
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_TRY(hipSetDevice(g->device));
-    if (g->d_kt) {
-        HIP_TRY(hipDeviceSynchronize());  // no batch may still read it
-        (void)hipFree(g->d_kt);
-        g->d_kt = nullptr;
-        g->kt_k = 0;
-    }
-    if (k == 0) return SMEM_OK;
-    const uint64_t n = ((1ull << (2 * (k + 1))) - 4) / 3;  // levels 1..k
-    uint4* p = nullptr;
-    hipError_t e = hipMalloc(&p, n * sizeof(uint4));
-    if (e != hipSuccess) return fail(SMEM_E_NOMEM, "smem_gpu_set_kmer_table: hipMalloc", e);
-    e = smem_launch_kmer_table(g->d_occ64, g->primary, g->L2, k, p, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return fail(SMEM_E_DEVICE, "smem_gpu_set_kmer_table: build", e);
-    }
-    g->d_kt = p;
-    g->kt_k = k;
+    return kmer_table_build(g, k, "smem_gpu_set_kmer_table");
+}
+
+int smem_gpu_kmer_facts(smem_gpu_t* g, int* k, int* depth, uint64_t* minsz, int n_minsz) {
+    if (!g) return SMEM_E_ARG;
+    gpu_wait(g);
+    if (k) *k = g->kt_k;
+    if (depth) *depth = g->kt_d;
+    for (int l = 0; minsz && l < n_minsz; ++l) minsz[l] = l < 16 ? g->kt_min[l] : 0;
     return SMEM_OK;
 }
 
@@ -1119,6 +1212,10 @@ static void fill_params(smem_batch_t* b, const smem_opt_t* o, smem::SeedParams& 
     P.split_len_init = (int)(o->min_seed_len * o->split_factor + .499);
     P.split_width = o->split_width;
     P.start_width = o->start_width;
+    // the depth below which the default kernel keeps a call's entries virtual: a re-seeding call's min_intv
+    // is its match's size + 1, at most split_width + 1 (software/bwamem.c:272-276)
+    P.kt_dp0 = smem_kmer_call_depth(b->g->kt_min, b->g->kt_d, o->start_width);
+    P.kt_dp1 = smem_kmer_call_depth(b->g->kt_min, b->g->kt_d, (int64_t)std::max(o->split_width, 0) + 1);
     P.scratch = b->d_scratch.p;
     P.cap_list = b->cap_list;
     const char* dbg = getenv("SMEM_DEBUG_FLAGS");
@@ -1159,7 +1256,7 @@ static int batch_run_impl(smem_batch_t* b, const smem_opt_t* opt) {
     P.scratch = b->d_scratch.p;
     HIP_TRY(hipMemsetAsync(b->d_ctr.p, 0, 12 * sizeof(int32_t), b->st));
     HIP_TRY(hipEventRecord(b->ev[0], b->st));
-    if (n > 0) HIP_TRY(smem_launch_seed(&P, grid, 256, g->variant, b->st));
+    if (n > 0) HIP_TRY(smem_launch_seed(&P, grid, 256, seed_run_variant(g), b->st));
     // The sizes were written by the seeding kernel as each read completed: the offset scans go
     // straight behind it, their totals land beside the counters, and one copy and one wait bring
     // back the overflow count and both totals.  (After an overflow the scans run again: the
@@ -1198,7 +1295,7 @@ static int batch_run_impl(smem_batch_t* b, const smem_opt_t* opt) {
             Q.ovf_items = b->d_ovf_items2.p;
             HIP_TRY(hipMemsetAsync(b->d_ctr.p + 2, 0, 2 * sizeof(int32_t), b->st));
             const int ql = std::min(b->lanes, (n_ovf * seed_lanes_per_read(g->variant) + 255) / 256 * 256);
-            HIP_TRY(smem_launch_seed(&Q, std::max(1, ql / 256), 256, g->variant, b->st));
+            HIP_TRY(smem_launch_seed(&Q, std::max(1, ql / 256), 256, seed_run_variant(g), b->st));
             HIP_TRY(hipMemcpyAsync(b->h_ctr.p, b->d_ctr.p, 12 * sizeof(int32_t), hipMemcpyDeviceToHost, b->st));
             HIP_TRY(hipStreamSynchronize(b->st));
             if (b->h_ctr.p[3] == 0) break;

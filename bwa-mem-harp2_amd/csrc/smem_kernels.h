@@ -50,6 +50,8 @@ struct SeedParams {
     uint64_t* tspan;           // [0] max of ~(wave start), [1] max of wave end (s_memrealtime), nullptr: none
     const uint4* kt;           // k-mer bi-interval table (smem_launch_kmer_table; variant 23), nullptr: none
     int kt_k;                  // its longest k-mer
+    int kt_dp0, kt_dp1;        // seed_wp_kernel SKIP: the probe depth of calls with min_intv = start_width and of
+                               // re-seeding calls (min_intv <= split_width + 1): smem_kmer_call_depth, < kt_k; 0: none
 };
 
 // bwt_sa over the seeding output (software/bwamem.c:462-474, software/bwt.c:104-114)
@@ -100,6 +102,8 @@ hipError_t smem_launch_occ192(const uint32_t* occ64, uint64_t n_blocks, uint32_t
 // packed entries (x0, x1, x2 low words, bits 32-33 in word 3), x2 = 0 when absent
 hipError_t smem_launch_kmer_table(const uint32_t* occ64, uint64_t primary, const uint64_t* L2, int k, uint4* kt,
                                   hipStream_t st);
+// mn[L] = the smallest x2 of table level L, L = 1..k (mn: k + 1 device words)
+hipError_t smem_launch_kmer_min(const uint4* kt, int k, unsigned long long* mn, hipStream_t st);
 hipError_t smem_launch_finalize(const smem::FinalizeParams* F, int write, hipStream_t st);
 hipError_t smem_launch_fill_i32(int32_t* p, int32_t v, int n, hipStream_t st);
 hipError_t smem_launch_pack_intv(const smem::Intv* in, uint64_t n, uint4* out, hipStream_t st);

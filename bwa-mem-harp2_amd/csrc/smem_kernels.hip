@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include "smem_kernels.h"
 
 namespace smem {
@@ -77,6 +78,22 @@ __device__ __forceinline__ int qsel(uint32_t o0, int i, const uint4& qv) {
     return (int)((w >> ((a & 3) * 8)) & 0xff);
 }
 
+// the 16 bases of a query window as 2-bit codes, the first base highest (4 bytes b0..b3 of a word times
+// 2^30 + 2^20 + 2^10 + 1 leave b0 << 6 | b1 << 4 | b2 << 2 | b3 in the top byte; the other partial products
+// fall on bits of their own below it), and the mask of its ambiguous bases (byte > 3), bit j = base j
+__device__ __forceinline__ uint32_t win_codes(const uint4& qv) {
+    auto c = [](uint32_t w) { return ((w & 0x03030303u) * 0x40100401u) >> 24; };
+    return c(qv.x) << 24 | c(qv.y) << 16 | c(qv.z) << 8 | c(qv.w);
+}
+__device__ __forceinline__ uint32_t win_ambig(const uint4& qv) {
+    auto n = [](uint32_t w) {
+        const uint32_t t = w & 0xFCFCFCFCu;
+        const uint32_t y = (((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;  // bit 7 of every byte that is not 0
+        return ((y >> 7) * 0x01020408u) >> 24;
+    };
+    return n(qv.x) | n(qv.y) << 4 | n(qv.z) << 8 | n(qv.w) << 12;
+}
+
 enum Phase : int {
     P_BWD_RES = 0,  // consume a backward extend        (software/bwt.c:815-825)
     P_BWD_J,        // next prev[j] / end of a step      (software/bwt.c:812, 827-828)
@@ -91,6 +108,9 @@ enum Phase : int {
     P_FETCH,        // next read from the work counter
     P_BWD_WAIT,     // seed_wp_kernel: the wave is extending the step's entries
     P_BWD_DONE,     // seed_wp_kernel: every entry of the step extended
+    P_KSCAN,        // seed_wp_kernel SKIP: collect the call's first bases for the start probe
+    P_KRES,         // seed_wp_kernel SKIP: consume the start probe (the forward string of d bases)
+    P_KEND,         // seed_wp_kernel SKIP: consume the probe of the longest virtual entry at a call's end
     P_EXIT
 };
 
@@ -273,7 +293,7 @@ struct WpWave {
     uint4 e[NL][OWN];     // owners' lists: index k < NL at slot (lr - k) mod NL
     // step descriptors, by owner lane (DPOS: by the task position where the owner's entries start):
     // j, curr_n, prev_off, c | lr << 2 | last_x2 bits 32-33 << 8 | i << 10; min_intv, last_x2 low word,
-    // prev_n (DPOS: the owner lane), kb
+    // prev_n (DPOS: the owner lane; SKIP: | dp << 24), kc
     uint4 d0[DPOS ? 64 : OWN];
     uint4 d1[DPOS ? 64 : OWN];
     uint4 q[OWN];         // query windows (LDS-DMA landing slots)
@@ -358,12 +378,32 @@ __device__ __forceinline__ void wave_lds_fence() {
 // exactly when P_FWD has just asked for the extend), 64 the selects by base as two bit tests (sel4b;
 // out: sel4's compare chain, which compiles to a branch tree), 128 the query byte by one bit test and
 // a 64-bit shift (out: qsel's compare chain, a branch tree again)
-template <int OWN, int NL, int PRIO, int WPE = 3, bool PAIR = false, bool KT = false, bool DPOS = false, int OPT = 15>
-__global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
+// SKIP (with KT; DESIGN.md §5 "Virtual short entries"): the entries of a call whose strings are shorter
+// than dp bases are not stored and not extended.  With D the largest level below the table's depth at
+// which every string of D + 1 bases occurs and minsz[L] the smallest interval size of level L, dp is a
+// level <= D with minsz[dp] >= min_intv: the host passes one for a read's first calls (P.kt_dp0) and one
+// for its re-seeding calls (P.kt_dp1; smem_gpu.cpp fill_params).  Up to dp bases every forward extend
+// changes the size and none falls below min_intv, so a call starts with one probe of its first
+// d = min(dp, bases before an ambiguous one or the read's end) bases and counts the d - 1 shorter
+// forward entries as virtual (nv: the forward lengths 1..nv).  In a backward step a virtual entry whose
+// string stays below dp bases survives and is never a duplicate (the entry kept before it is a proper
+// right extension, strictly smaller), so it gets no task; the one whose string reaches exactly dp bases
+// is probed (the step's last task, after the real entries) and is real from then on.  A call that ends
+// (i == -1 or an ambiguous base) with only virtual entries left probes the longest at its length for
+// the record.  dp < 2: the call runs the plain path.  (No loops over bases or levels in the owners'
+// blocks, and no further WP_EMIT site: the first version had them and doubled the launch's SALU)
+// (the body of both kernels below: seed_wp_kernel keeps its eight parameters and its symbol)
+template <int OWN, int NL, int PRIO, int WPE, bool PAIR, bool KT, bool DPOS, int OPT, bool SKIP>
+__device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
     constexpr int DIET = ~OPT;  // bits 16-128 of OPT take an arm of the diet out
+    static_assert(!SKIP || (KT && !PAIR && !DPOS), "SKIP probes the k-mer table and keeps prev_n | dp << 24 in the descriptor");
     static_assert(!(DPOS && PAIR), "DPOS keeps the owner lane where PAIR keeps prev_n");
     constexpr uint32_t PR = PAIR ? 2u : 1u;  // entries per worker lane
     const int K = KT && P.kt ? P.kt_k : 0;
+    // SKIP: the probe depth of a read's first calls (min_intv = start_width) and of its re-seeding calls
+    // (min_intv <= split_width + 1), chosen on the host (smem_kmer_call_depth); both below the table's depth
+    const uint32_t DP0 = SKIP && K > 0 && P.kt_dp0 < K ? (uint32_t)P.kt_dp0 : 0u;
+    const uint32_t DP1 = SKIP && K > 0 && P.kt_dp1 < K ? (uint32_t)P.kt_dp1 : 0u;
     static_assert(OWN >= 1 && OWN <= 64 && NL >= 2 && NL < 32, "owners per wave / list entries");
     __shared__ WpWave<OWN, NL, PAIR, DPOS> wlds[4];
     WpWave<OWN, NL, PAIR, DPOS>* L = &wlds[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
@@ -393,16 +433,18 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
     uint4 qv = {0, 0, 0, 0};
     uint32_t raw_n = 0, calls_n = 0;
     int start = 0, ori_start = 0;
-    int x = 0, min_intv = 1, middle = 0, i = 0, ret = 0, cur_c = 0;
+    int x = 0, min_intv = 1, middle = 0, i = 0, cur_c = 0;
     uint32_t j = 0;
-    uint32_t kc = 0, kb = 0;  // KT: the forward string's codes, the K bases from backward position i
+    uint32_t kc = 0;  // KT: forward, the string's codes; backward, the K bases from position i (one register: never both)
+    uint32_t nv = 0;  // SKIP: virtual entries left (forward lengths 1..nv)
     uint64_t ik0 = 0, ik1 = 0, ik2 = 0;
-    uint32_t ikend = 0;
-    uint32_t fwd_n = 0, prev_off = 0, prev_n = 0, curr_n = 0;
+    uint32_t ikend = 0;  // ik's end; from the end of the forward phase on, bwt_smem1's return value
+    // fwd_n is prev_off as well: forward, the entries pushed; backward, where prev[NL ..] sits in the arena
+    uint32_t fwd_n = 0, prev_n = 0, curr_n = 0;
     uint32_t lr = 0;           // forward: the ring position; backward: the slot of list index 0
-    uint32_t fail0 = 0;        // entry 0 of the current step failed (its SMEM candidate)
+    uint32_t fail0 = 0;        // bit 0: entry 0 of the current step failed (its SMEM candidate); SKIP, bit 1: the step has a probe (WP_VP)
     uint64_t last_x2 = 0;      // size of the last entry kept in curr (dedup across chunks of a step)
-    uint32_t mem_n = 0, mem_last_start = 0;
+    uint32_t mem_last_start = ~0u;  // the start of the call's last record (~0: none yet, mem->n == 0)
     uint32_t max_len = 0, max_x2 = 0, max_mid = 0;
     uint4 head = {0, 0, 0, 0};  // prev[0] of the current step
     uint64_t na = 0, nb = 0, ns = 0;
@@ -443,7 +485,6 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                 ++raw_n;                                                                                     \
             }                                                                                                \
         }                                                                                                    \
-        ++mem_n;                                                                                             \
         mem_last_start = b_;                                                                                 \
         if (!middle && en_ - b_ >= max_len) {                                                                \
             max_len = en_ - b_;                                                                              \
@@ -487,6 +528,9 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
     {                                    \
         if constexpr (!(DIET & 32)) out = true; \
     }
+// SKIP: this step materialises a virtual entry (the longest one's string reaches dp bases at position i)
+#define WP_DP() (middle ? DP1 : DP0)
+#define WP_VP() (SKIP && nv != 0 && nv + (uint32_t)(x - i) == WP_DP())
 // one forward push (software/bwt.c:797, 802): the ring's oldest entry moves to the arena first
 #define WP_PUSH()                                                                                                \
     {                                                                                                            \
@@ -528,11 +572,24 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         // blocks, without the per-entry backward block) ----
         [[maybe_unused]] bool out = false;
         if (phase != P_EXIT) {
+            if constexpr (SKIP) {  // the owner's own probe has landed (na: the x[1] side, nb: x[0])
+                if (phase == P_KRES) {  // the forward string of i - x bases; the shorter ones stay virtual
+                    ik0 = nb; ik1 = na; ik2 = ns;
+                    ikend = (uint32_t)i;
+                    nv = (uint32_t)(i - x) - 1;
+                    phase = P_FWD;
+                } else if (phase == P_KEND) {  // the longest virtual entry, now prev[0]: P_BWD_STEP emits it
+                    head = pack_p(nb, na, ns, (uint32_t)x + nv);
+                    nv = 0;
+                    prev_n = 1;
+                    phase = P_BWD_STEP;
+                }
+            }
             if (phase == P_SMEM_END) {
                 if (!middle) {  // software/bwamem.c:261-272
-                    start = ret;
+                    start = (int)ikend;
                     const int split_len = P.split_len_init < len ? P.split_len_init : len;
-                    if (mem_n > 0 && split_len > 0 && (int)max_len >= split_len &&
+                    if (mem_last_start != ~0u && split_len > 0 && (int)max_len >= split_len &&
                         (uint64_t)max_x2 <= (uint64_t)(int64_t)P.split_width) {
                         x = (int)max_mid;  // re-seed from the middle (software/bwamem.c:272-278)
                         min_intv = (int)(max_x2 + 1);
@@ -565,7 +622,14 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                     calls_n = 0;
                     start = 0;
                     if (len < P.min_seed_len) {  // mem_chain's guard (software/bwamem.c:600)
-                        *reinterpret_cast<uint4*>(P.sizes + 2 * (uint64_t)rid) = make_uint4(0, 0, 0, 0);
+                        // (zeros made here, opaque to the compiler: as a constant it hoisted them out of the loop
+                        // and, at 128 VGPRs, into a spill slot -- the skipping kernel then 128 VGPRs + 4 spilled
+                        // (20 B of scratch a lane) instead of 128 + 0, the plain one 122 VGPRs instead of 118 and no
+                        // spill either way; hipcc --cuda-device-only -S, ROCm 7.2.  A compiler that spills here again only costs this
+                        // rare path a scratch load: check the .vgpr_spill_count the build reports)
+                        uint32_t z;
+                        asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+                        *reinterpret_cast<uint4*>(P.sizes + 2 * (uint64_t)rid) = make_uint4(z, z, z, z);
                         WP_OUT();
                     } else {
                         phase = P_NEXT2;
@@ -607,10 +671,10 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                     qwant = QBLK(x);
                     WP_OUT();
                 } else {
-                    mem_n = 0;
+                    mem_last_start = ~0u;
                     const int qx = qsel<(DIET & 128) != 0>(o0, x, qv);
                     if (qx > 3) {
-                        ret = x + 1;
+                        ikend = (uint32_t)(x + 1);
                         phase = P_SMEM_END;
                     } else {
                         if (min_intv < 1) min_intv = 1;
@@ -629,17 +693,62 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                         lr = 0;
                         i = x + 1;
                         phase = P_FWD;
+                        if constexpr (SKIP) {
+                            nv = 0;
+                            if (WP_DP() >= 2) phase = P_KSCAN;
+                        }
+                    }
+                }
+            }
+            if constexpr (SKIP) {
+                // the codes of q[x, i) are in kc; the window's bases from i, up to the call's depth, the read's end
+                // or an ambiguous base, in one go (no loop: the whole wave would walk it)
+                if (phase == P_KSCAN) {
+                    bool done = true;
+                    if (i < len && (uint32_t)(i - x) < WP_DP()) {
+                        done = false;
+                        if (QBLK(i) != qb) {
+                            qwant = QBLK(i);
+                            WP_OUT();
+                        } else {
+                            const uint32_t off = (o0 + (uint32_t)i) & 15u;
+                            const uint32_t rem = min(WP_DP() - (uint32_t)(i - x), (uint32_t)(len - i));
+                            const uint32_t inwin = min(rem, 16u - off);
+                            const uint32_t nm = win_ambig(qv) >> off;
+                            const uint32_t nfree = nm ? (uint32_t)__builtin_ctz(nm) : 16u;  // bases before an ambiguous one
+                            const uint32_t take = min(inwin, nfree);
+                            if (take) {
+                                kc = kc << (2 * take) | (win_codes(qv) << (2 * off)) >> (32 - 2 * take);
+                                i += (int)take;
+                            }
+                            if (take == inwin && inwin < rem) {  // the rest is in the next window
+                                qwant = QBLK(i);
+                                WP_OUT();
+                            } else {
+                                done = true;
+                            }
+                        }
+                    }
+                    if (done) {
+                        if (i - x >= 2) {
+                            if (i < len) qwant = QBLK(i);
+                            phase = P_KRES;  // -> the probe of q[x, i), on this lane
+                            WP_OUT();
+                        } else {
+                            phase = P_FWD;
+                        }
                     }
                 }
             }
             if (phase == P_BWD_DONE) {  // every entry of step i extended (software/bwt.c:815-828)
-                if (fail0 && (mem_n == 0 || (uint32_t)(i + 1) < mem_last_start)) WP_EMIT(head);
+                if ((fail0 & 1u) && (uint32_t)(i + 1) < mem_last_start) WP_EMIT(head);
                 if (phase == P_BWD_DONE) {
-                    if (curr_n == 0) {  // software/bwt.c:827
+                    if (curr_n == 0 && (!SKIP || nv == 0)) {  // software/bwt.c:827 (virtual entries are in curr too)
                         phase = P_SMEM_END;
                     } else {            // :828 swap, next position
+                        if constexpr (SKIP) nv -= fail0 >> 1;  // the step's probe made the longest virtual entry real
                         prev_n = curr_n;
-                        prev_off = cap;
+                        fwd_n = cap;
                         head = L->e[lr][me];  // curr[0]: index 0 sits in slot lr
                         --i;
                         phase = P_BWD_STEP;
@@ -689,13 +798,12 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             }
             if (phase == P_FWD_DONE) {  // software/bwt.c:805-808 (the ring read backwards is the reversal)
                 head = pack_p(ik0, ik1, ik2, ikend);  // the last push: prev[0]
-                ret = (int)ikend;
                 if constexpr (KT) {  // the K bases from x (those past the forward string are never read)
                     const uint32_t lf = ikend - (uint32_t)x;
-                    kb = lf >= (uint32_t)K ? kc : kc << (2 * ((uint32_t)K - lf));
+                    if (lf < (uint32_t)K) kc <<= 2 * ((uint32_t)K - lf);
                 }
-                prev_off = cap - fwd_n;
                 prev_n = fwd_n;
+                fwd_n = cap - fwd_n;
                 lr = lr == 0 ? (uint32_t)NL - 1 : lr - 1;  // slot of the last push
                 i = x - 1;
                 phase = P_BWD_STEP;
@@ -710,14 +818,28 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                     if (cur_c >= 0) {
                         j = 0;
                         curr_n = 0;
-                        fail0 = 0;
-                        if constexpr (KT) kb = (uint32_t)cur_c << (2 * (K - 1)) | kb >> 2;
+                        fail0 = WP_VP() ? 2u : 0u;
+                        if constexpr (KT) {
+                            if (K > 0) kc = (uint32_t)cur_c << (2 * (K - 1)) | kc >> 2;
+                        }
                         if (i > 0) qwant = QBLK(i - 1);  // the next step's base
                         phase = P_BWD_WAIT;               // -> the wave extends the step's entries
+                        if constexpr (SKIP) {
+                            // only virtual entries are left and none reaches dp bases: they all survive, the
+                            // step changes nothing (rare: one pass a step)
+                            if (prev_n == 0 && !fail0) {
+                                --i;
+                                phase = P_BWD_STEP;
+                                WP_OUT();
+                            }
+                        }
                     } else {
                         // nothing extends: prev[0] is the only candidate (software/bwt.c:816-819)
                         phase = P_SMEM_END;
-                        if (mem_n == 0 || (uint32_t)(i + 1) < mem_last_start) WP_EMIT(head);
+                        if ((uint32_t)(i + 1) < mem_last_start) {
+                            if (SKIP && prev_n == 0 && nv != 0) phase = P_KEND;  // prev[0] is virtual: -> its probe, on this lane
+                            else WP_EMIT(head);
+                        }
                     }
                 }
             }
@@ -725,13 +847,15 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         // ---- uniform section ----
         if (!__any(phase != P_EXIT)) break;
         // (a lane is at P_FWD_RES here only when P_FWD has just set it: the P_FWD_RES block always leaves it)
-        const bool fwdreq = ((DIET & 32) || out) && phase == P_FWD_RES;
-        const uint32_t rem = phase == P_BWD_WAIT ? prev_n - j : 0u;
+        // (the same holds for SKIP's own probes, P_KRES / P_KEND: a lane that extends or probes for itself)
+        const bool ownp = SKIP && (phase == P_KRES || phase == P_KEND);
+        const bool fwdreq = ((DIET & 32) || out) && (phase == P_FWD_RES || ownp);
+        const uint32_t rem = phase == P_BWD_WAIT ? prev_n + (SKIP ? fail0 >> 1 : 0u) - j : 0u;
         const uint32_t slots = (rem + PR - 1) / PR;  // worker lanes the step still needs
         if (!DPOS && rem) {  // what a worker needs of this owner's step
-            L->d0[me] = make_uint4(j, curr_n, prev_off,
+            L->d0[me] = make_uint4(j, curr_n, fwd_n,
                                    (uint32_t)cur_c | lr << 2 | (uint32_t)(last_x2 >> 32) << 8 | (uint32_t)i << 10);
-            L->d1[me] = make_uint4((uint32_t)min_intv, (uint32_t)last_x2, prev_n, kb);
+            L->d1[me] = make_uint4((uint32_t)min_intv, (uint32_t)last_x2, SKIP ? prev_n | WP_DP() << 24 : prev_n, kc);
         }
         // the owners' remaining entries laid out in lane order over the free lanes
         const uint32_t incl = wave_scan_add(slots);
@@ -746,9 +870,9 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         uint64_t marks;
         if constexpr (DPOS) {
             if (take) {  // the descriptor where the owner's entries start
-                L->d0[excl] = make_uint4(j, curr_n, prev_off,
+                L->d0[excl] = make_uint4(j, curr_n, fwd_n,
                                          (uint32_t)cur_c | lr << 2 | (uint32_t)(last_x2 >> 32) << 8 | (uint32_t)i << 10);
-                L->d1[excl] = make_uint4((uint32_t)min_intv, (uint32_t)last_x2, (uint32_t)me, kb);
+                L->d1[excl] = make_uint4((uint32_t)min_intv, (uint32_t)last_x2, (uint32_t)me, kc);
             }
             if (freel) L->tabP[rank] = (uint8_t)me;
             const uint32_t mlo = wave_or(take && excl < 32 ? 1u << excl : 0u);
@@ -779,6 +903,7 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         bool has2 = false;
         uint4 w0 = WP_IDLE128(), w1 = WP_IDLE128(), ent = WP_IDLE128(), ent2 = {0, 0, 0, 0};
         bool far = false, far2 = false;  // the entry (PAIR: the second) is in the owner's arena
+        bool isp = false;                // SKIP: the task is the step's probe (list index prev_n), not an entry
         if (worker) {
             s = (uint32_t)hibit64(marks & ((2ull << rank) - 1ull));  // the segment holding task `rank`
             if constexpr (DPOS) {
@@ -792,10 +917,11 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             }
             jj = w0.x + PR * (rank - s);
             lro = (w0.w >> 2) & 31u;
-            if (jj < (uint32_t)NL) {
+            if constexpr (SKIP) isp = jj == (w1.z & 0xFFFFFFu);
+            if (jj < (uint32_t)NL) {  // (a probe task reads a slot no entry is in: only its end is used, set below)
                 ent = L->e[WSLOT(lro, jj)][o];
             } else if constexpr (OPT & 2) {
-                far = true;
+                far = !isp;
             } else {
                 const PIntv* obp = reinterpret_cast<const PIntv*>(P.scratch + (wown + o) * 2ull * cap);
                 const uint32_t at = w0.z + jj;
@@ -815,6 +941,9 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
                     }
                 }
             }
+        }
+        if constexpr (SKIP) {  // the probed string ends at i + dp
+            if (isp) ent.w = ((w0.w >> 10) + (w1.z >> 24)) << 6;
         }
         const bool ld_q = qwant != qb && qwant != ~0u;
         if constexpr (!(OPT & 4)) WP_ISSUE();
@@ -852,7 +981,17 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
         uint4 k0 = WP_IDLE128(), k1 = WP_IDLE128(), l0 = WP_IDLE128(), l1 = WP_IDLE128();
         // KT: a result of at most K bases from the table (forward: q[x, i]; backward: q[i, end))
         bool ktp = false;
-        if constexpr (KT) {
+        if constexpr (SKIP) {  // the only probes: an owner's own (start / end of a call), a step's last task
+            if (ownp || isp) {
+                int lq = ownp ? (phase == P_KRES ? i - x : (int)nv + x - i - 1) : (int)(w1.z >> 24);
+                lq = lq < 1 ? 1 : (lq > K ? K : lq);  // (only a broken state is clipped: the probe stays in the table)
+                const uint32_t code = (ownp ? (phase == P_KRES ? kc : kc >> (2 * (K - lq))) : w1.w >> (2 * (K - lq))) &
+                                      ((1u << (2 * lq)) - 1u);
+                // level lq starts at (4^lq - 4) / 3 = 0b0101..01 (lq ones) - 1
+                k0 = P.kt[(0x55555555u >> (32 - 2 * lq)) - 1u + code];
+                ktp = true;
+            }
+        } else if constexpr (KT) {
             if (task && K > 0) {
                 const int lq = fwdreq ? i + 1 - x : (int)p_end(ent) - (int)(w0.w >> 10);
                 if (lq <= K) {
@@ -906,7 +1045,16 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             qv = L->q[me];
             qb = qwant;
         }
-        if (ktp) {  // forward: na is the x[1] side, backward: the x[0] side
+        if constexpr (SKIP) {  // one region: the few probe lanes take the table's entry by selects
+            if (task) {
+                const Bucket32 wk{k0, k1};
+                const Bucket32 wl = bl != bk ? Bucket32{l0, l1} : wk;
+                extend_counts64<false, (DIET & 64) != 0>(P, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
+                na = ktp ? (fwdreq ? p_x1(k0) : p_x0(k0)) : na;
+                nb = ktp ? (fwdreq ? p_x0(k0) : p_x1(k0)) : nb;
+                ns = ktp ? p_x2(k0) : ns;
+            }
+        } else if (ktp) {  // forward: na is the x[1] side, backward: the x[0] side
             na = fwdreq ? p_x1(k0) : p_x0(k0);
             nb = fwdreq ? p_x0(k0) : p_x1(k0);
             ns = p_x2(k0);
@@ -968,25 +1116,38 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
             const uint32_t pf = L->tabP[excl], pl = L->tabP[excl + take - 1];
             const uint64_t seg = ((2ull << pl) - 1ull) & ~((1ull << pf) - 1ull);
             const uint64_t km = kmask & seg, km2 = kmask2 & seg;
-            if (j == 0) fail0 = !((smask >> pf) & 1);
+            if (j == 0) fail0 = (SKIP ? fail0 & 2u : 0u) | !((smask >> pf) & 1);
             if (km | km2) {  // the last entry kept: the highest lane's second entry if it kept one
                 const int hb = hibit64(km | km2);
                 last_x2 = ((km2 >> hb) & 1) ? RES[hb] : (PAIR ? L->res1[hb] : RES[hb]);
             }
             curr_n += (uint32_t)(__popcll(km) + __popcll(km2));
             j += min(rem, PR * take);
-            if (j == prev_n) phase = P_BWD_DONE;
+            if (j == prev_n + (SKIP ? fail0 >> 1 : 0u)) phase = P_BWD_DONE;
         }
         wave_lds_fence();  // this iteration's LDS reads before the next one's writes
     }
 #undef WP_EMIT
 #undef WP_PUSH
+#undef WP_VP
+#undef WP_DP
 #undef WP_OUT
 #undef WP_IDLE32
 #undef WP_IDLE128
 #undef WSLOT
 #undef QBLK
     if (P.tspan && me == 0) atomicMax(reinterpret_cast<unsigned long long*>(P.tspan) + 1, (unsigned long long)rtstamp());
+}
+
+template <int OWN, int NL, int PRIO, int WPE = 3, bool PAIR = false, bool KT = false, bool DPOS = false, int OPT = 15>
+__global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
+    seed_wp_body<OWN, NL, PRIO, WPE, PAIR, KT, DPOS, OPT, false>(P);
+}
+
+// the same with the short entries virtual (SKIP; reads the k-mer table, every OPT bit)
+template <int OWN, int NL, int PRIO, int WPE>
+__global__ __launch_bounds__(256, WPE) void seed_wp_kernel_skip(SeedParams P) {
+    seed_wp_body<OWN, NL, PRIO, WPE, false, true, false, 15, true>(P);
 }
 
 // Raw logs -> the lists smem_next2 returns: reverse each bwt_smem1 output
@@ -1067,18 +1228,20 @@ __global__ void ovf_slot_kernel(const int32_t* __restrict__ items, int n_ovf, in
 }  // namespace smem
 
 // ------------------------------------------------------------ host launchers
-// The product build instantiates the default kernel (seed_wp_kernel variant 49;
-// 0 names it too) and its k-mer table twin (54).  The other seed_wp_kernel
-// shapes and OPT-bit twins (40-67 other than 49 / 54;
+// The product build instantiates the kernel a handle on its default runs (seed_wp_kernel
+// variant 68: 49's shape with the short entries virtual; smem_gpu.cpp seed_run_variant),
+// 49 itself (the plain kernel: a handle without a usable k-mer table, or 49 asked for by
+// number) and 49's k-mer table twin (54).  The other seed_wp_kernel
+// shapes and OPT-bit twins (40-70 other than 49 / 54 / 68;
 // DESIGN.md §5) are compiled only with SMEM_AB_VARIANTS (make AB=1): the
 // library ships no kernel whose numbers are already recorded.  (Rounds 1-4's
 // one-lane-per-read seed_kernel, variants 2-31, wrote the raw log format of
 // its time and left with it; its numbers are in DESIGN.md §5.)
 extern "C" int smem_seed_variant_built(int variant) {
 #ifdef SMEM_AB_VARIANTS
-    return variant == 0 || (variant >= 40 && variant <= 67);
+    return variant == 0 || (variant >= 40 && variant <= 70);
 #else
-    return variant == 0 || variant == 49 || variant == 54;
+    return variant == 0 || variant == 49 || variant == 54 || variant == 68;
 #endif
 }
 
@@ -1125,11 +1288,16 @@ extern "C" hipError_t smem_launch_seed(const smem::SeedParams* P, int grid, int 
         case 65: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 79>), dim3(grid), dim3(block), 0, st, *P); break;
         case 66: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 143>), dim3(grid), dim3(block), 0, st, *P); break;
         case 67: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 255>), dim3(grid), dim3(block), 0, st, *P); break;
+        // 69-70: 68 (virtual short entries) with more owners and shorter lists: <32, 12>, <28, 14>
+        case 69: hipLaunchKernelGGL((smem::seed_wp_kernel_skip<32, 12, 1, 4>), dim3(grid), dim3(block), 0, st, *P); break;
+        case 70: hipLaunchKernelGGL((smem::seed_wp_kernel_skip<28, 14, 1, 4>), dim3(grid), dim3(block), 0, st, *P); break;
 #endif
         // 54: the default's shape with the k-mer table (KT; smem_gpu_set_kmer_table, no table: plain)
         case 54: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        // default (49; 0 names it): seed_wp_kernel<24 owners per wave, 18 LDS list entries per owner,
-        // wave priority, 4 blocks per CU> with every OPT bit
+        // 68: 49's shape with the short entries virtual (SKIP; no table: 49's path)
+        case 68: hipLaunchKernelGGL((smem::seed_wp_kernel_skip<24, 18, 1, 4>), dim3(grid), dim3(block), 0, st, *P); break;
+        // 49 (and any number this build does not have): seed_wp_kernel<24 owners per wave, 18 LDS list
+        // entries per owner, wave priority, 4 blocks per CU> with every OPT bit
         default: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4>), dim3(grid), dim3(block), 0, st, *P); break;
     }
     return hipGetLastError();
@@ -1349,6 +1517,25 @@ __global__ __launch_bounds__(256) void kmer_table_kernel(SeedParams P, uint4* __
     }
 }
 
+// the smallest interval size of table level L (0: a string of L bases is absent) into mn[L], which the
+// host presets to ~0: each thread the minimum of a strided share, each wave one atomic
+__global__ __launch_bounds__(256) void kmer_level_min_kernel(const uint4* __restrict__ kt, int L,
+                                                             unsigned long long* __restrict__ mn) {
+    const uint64_t n = 1ull << (2 * L);
+    const uint4* lev = kt + (n - 4) / 3;
+    unsigned long long m = ~0ull;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long s = p_x2(lev[w]);
+        m = s < m ? s : m;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long t = __shfl_xor(m, d, 64);
+        m = t < m ? t : m;
+    }
+    if ((threadIdx.x & 63) == 0) atomicMin(mn + L, m);
+}
+
 // Occ64 -> Occ192 (see rank192); one thread per 64-B line of 192 symbols
 __global__ __launch_bounds__(256) void occ192_kernel(const uint32_t* __restrict__ occ64, uint64_t n_blocks,
                                                       uint64_t n_lines, uint32_t* __restrict__ out) {
@@ -1397,6 +1584,18 @@ extern "C" hipError_t smem_launch_kmer_table(const uint32_t* occ64, uint64_t pri
     for (int L = 2; L <= k && e == hipSuccess; ++L) {
         const uint64_t n = 1ull << (2 * (L - 1));
         hipLaunchKernelGGL(smem::kmer_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, kt, L);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+extern "C" hipError_t smem_launch_kmer_min(const uint4* kt, int k, unsigned long long* mn, hipStream_t st) {
+    if (k < 1 || k > 15) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(mn, 0xFF, sizeof(unsigned long long) * (size_t)(k + 1), st);
+    for (int L = 1; L <= k && e == hipSuccess; ++L) {
+        const uint64_t n = 1ull << (2 * L);
+        const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(smem::kmer_level_min_kernel, dim3(grid), dim3(256), 0, st, kt, L, mn);
         e = hipGetLastError();
     }
     return e;

@@ -26,6 +26,7 @@ EXPORTED = [
     "smem_batch_create", "smem_batch_destroy", "smem_batch_set_reads", "smem_batch_set_reads_packed",
     "smem_batch_run", "smem_batch_fetch", "smem_batch_read", "smem_batch_results", "smem_batch_stats",
     "smem_gpu_set_lanes_per_cu", "smem_gpu_set_intv_cap", "smem_gpu_set_kernel_variant", "smem_gpu_get_kernel_variant", "smem_gpu_grid_reads", "smem_gpu_set_kmer_table", "smem_batch_debug", "smem_strerror",
+    "smem_gpu_kmer_facts", "smem_gpu_seed_kernel", "smem_kmer_depth", "smem_kmer_call_depth",
     "smem_gpu_build_id",
     "smem_bwt_build_sa", "smem_bwt_build_gpu_sa", "smem_sa_read", "smem_sa_write", "smem_sa_free", "smem_gpu_load_sa",
     "smem_batch_sa", "smem_batch_sa_results",
@@ -281,6 +282,15 @@ def load() -> C.CDLL:
     lib.smem_gpu_grid_reads.argtypes = [C.c_void_p]
     lib.smem_gpu_grid_reads.restype = C.c_int
     lib.smem_gpu_set_kmer_table.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(lib, "smem_gpu_kmer_facts"):  # absent from A/B libraries built before the virtual entries
+        lib.smem_gpu_kmer_facts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int]
+        lib.smem_gpu_kmer_facts.restype = C.c_int
+        lib.smem_gpu_seed_kernel.argtypes = [C.c_void_p]
+        lib.smem_gpu_seed_kernel.restype = C.c_int
+        lib.smem_kmer_depth.argtypes = [C.c_void_p, C.c_int]
+        lib.smem_kmer_depth.restype = C.c_int
+        lib.smem_kmer_call_depth.argtypes = [C.c_void_p, C.c_int, C.c_int64]
+        lib.smem_kmer_call_depth.restype = C.c_int
     if hasattr(lib, "smem_batch_debug"):  # absent from older A/B builds
         lib.smem_batch_debug.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     lib.smem_strerror.argtypes = [C.c_int]
@@ -579,6 +589,19 @@ class Gpu:
     def set_kmer_table(self, k: int) -> None:
         """Build (k = 1..15) or free (0) the device k-mer bi-interval table."""
         _check(load().smem_gpu_set_kmer_table(self._h, k), "smem_gpu_set_kmer_table")
+
+    def kmer_facts(self) -> dict:
+        """The k-mer table's facts (smem_gpu_kmer_facts): k its depth (0: none), D the largest level
+        such that every string of D + 1 bases occurs, minsz[L] the smallest interval size of level L."""
+        k, d = C.c_int(0), C.c_int(0)
+        mn = np.zeros(16, dtype=np.uint64)
+        _check(load().smem_gpu_kmer_facts(self._h, C.byref(k), C.byref(d), mn.ctypes.data, 16), "smem_gpu_kmer_facts")
+        return {"k": k.value, "D": d.value, "minsz": [int(v) for v in mn[:k.value + 1]]}
+
+    @property
+    def seed_kernel(self) -> int:
+        """The seeding-kernel instantiation the next launch runs (smem_gpu_seed_kernel)."""
+        return int(load().smem_gpu_seed_kernel(self._h))
 
     def load_sa(self, sa: "SA") -> None:
         _check(load().smem_gpu_load_sa(self._h, C.byref(sa._raw)), "smem_gpu_load_sa")

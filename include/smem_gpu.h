@@ -644,21 +644,50 @@ int  smem_gpu_set_intv_cap(smem_gpu_t *gpu, int cap_per_read);
  * extend result of at most k bases from the k-mer table (needs
  * smem_gpu_set_kmer_table) */
 int  smem_gpu_set_kernel_variant(smem_gpu_t *gpu, int variant);
-/* the seeding kernel variant the handle runs (0 given to the setter = the
+/* the seeding kernel variant the handle is set to (0 given to the setter = the
  * default, 49: seed_wp_kernel -- the backward steps' entries extended by the
  * whole wave and pruned by ballot / prefix rank (software/bwt.c:812-826), 24
  * reads owned per wave, 18 list entries per read in LDS, 4 blocks per CU.
- * A/B: 40 32 reads / 20 entries / 3 blocks; 41 32 / 16; 42 24 / 24; 43 = 40
+ * A handle left on the default runs that shape's instantiation 68, which
+ * keeps the entries whose strings the handle's k-mer table answers virtual
+ * (smem_gpu_kmer_facts), while it holds a table of depth >= 2;
+ * smem_gpu_seed_kernel returns the instantiation the next launch runs.
+ * 49 set by number (or SMEM_GPU_SEED_VARIANT=49) is the plain kernel, in every
+ * build, for A/B; 68 by number runs it whatever the table (none: 49's path).
+ * Mind the collision: the number this getter reports for a default handle (49)
+ * is also the plain kernel's, and bench.py / tools/traffic.py key the recorded
+ * counters (profiles/traffic*.json) by it.  The committed records hold kernel
+ * 68's counters at table depth 12 under "variant": 49, so the roofline and
+ * counter fields bench.py prints for a `--variant 49` run, or for a run with
+ * another SMEM_GPU_KMER_K, are those records', not that run's.
+ * A/B (make AB=1): 69, 70 = 68 with 32 reads / 12 entries, 28 / 14; 40 32 reads / 20 entries / 3 blocks; 41 32 / 16; 42 24 / 24; 43 = 40
  * without wave priority; 44 24 / 16 / 4 blocks; 45 32 / 12; 46 28 / 14; 47, 48
  * two entries per worker lane; 50 20 / 22; 51 = 44 without wave priority; 2:
  * the lane-per-read seed_kernel of rounds 1-4).  SMEM_GPU_SEED_VARIANT in the
  * environment sets the default of every handle opened afterwards. */
 int  smem_gpu_get_kernel_variant(const smem_gpu_t *gpu);
+int  smem_gpu_seed_kernel(smem_gpu_t *gpu);
 /* build (k = 1..15) or free (k = 0) the device table of the bi-intervals of
  * every string of 1..k bases, built on the device from the resident index:
  * 16 B x (4^(k+1) - 4) / 3 (k = 12: 358 MB, 14: 5.7 GB); a table of a string
  * is the interval bwt_extend reaches for it on any path (software/bwt.c:416-429) */
 int  smem_gpu_set_kmer_table(smem_gpu_t *gpu, int k);
+/* A handle builds this table for itself when the index is loaded (k = 12, or
+ * SMEM_GPU_KMER_K from the environment; no deeper than 4^k <= the index's
+ * length; k = 0 or a failed allocation: no table, the plain path), and
+ * smem_gpu_set_kmer_table replaces or removes it.  The table's facts: *k its
+ * depth (0: none), minsz[L] the smallest interval size among the strings of L
+ * bases (0: one is absent; L = 1..k, n_minsz words written), *depth the
+ * largest level D < k such that every string of D + 1 bases occurs.  A
+ * bwt_smem1 call skips the extends of strings of fewer than
+ * smem_kmer_call_depth(minsz, D, min_intv) bases, min_intv taken as
+ * start_width for a read's first calls and as split_width + 1 (the most a
+ * re-seeding call can ask for) for its re-seeding calls. */
+int  smem_gpu_kmer_facts(smem_gpu_t *gpu, int *k, int *depth, uint64_t *minsz, int n_minsz);
+/* the two choices above as host functions of a table's per-level minimum
+ * sizes mn[1..k] (mn[0] unused) */
+int  smem_kmer_depth(const uint64_t *mn, int k);
+int  smem_kmer_call_depth(const uint64_t *mn, int depth, int64_t min_intv);
 /* variant 9 (stamped diagnostic build): copy the per-wave cycle split
  * {advance, fetch, compute, iterations, active lanes, t0, t1, 0} of the last
  * run; returns the number of words copied or a negative code */
