@@ -313,6 +313,8 @@ struct smem_gpu {
     int kt_k = 0;
     int kt_d = 0;                   // the table's facts (kmer_facts): see SeedParams::kt_d, kt_min
     uint64_t kt_min[16] = {0};
+    uint64_t kt_min_next = 0;       // the smallest size of level kt_k + 1, which is reduced but not stored (0: a
+                                    // string is absent, or the level was not reduced: kt_k = 15)
     double kt_build_s = 0.0;        // seconds the table's build and reduction took
     uint64_t* d_sa = nullptr;       // sampled SA (smem_gpu_load_sa), n_sa + 1 words
     uint8_t* d_pac = nullptr;       // 2-bit forward strand (smem_gpu_load_pac)
@@ -938,6 +940,17 @@ int smem_kmer_call_depth(const uint64_t* mn, int D, int64_t min_intv) {
     return dp;
 }
 
+// the probe depth of a bwt_smem1 call on a table of k levels whose next level, k + 1, was reduced to its
+// smallest size min_next without being stored (0 or ~0: a string of k + 1 bases is absent, or the level is
+// unknown): the largest level L <= k with levels 1 .. L + 1 all complete and mn[L] >= min_intv.  Level
+// k + 1 complete makes D = k; else this is smem_kmer_call_depth(mn, smem_kmer_depth(mn, k), min_intv).
+// (mn holds 16 words, so level 16 is never vouched for: k = 15 stays at D <= 14)
+int smem_kmer_probe_depth(const uint64_t* mn, int k, uint64_t min_next, int64_t min_intv) {
+    int D = smem_kmer_depth(mn, k);
+    if (k >= 1 && k <= 14 && D == k - 1 && mn[k] > 0 && min_next > 0 && min_next != ~0ull) D = k;
+    return smem_kmer_call_depth(mn, D, min_intv);
+}
+
 // the table of 1..k bases and its facts on g's device (g->mu held, no batch running); k = 0 frees it
 static int kmer_table_build(smem_gpu_t* g, int k, const char* who) {
     if (g->d_kt) {
@@ -945,6 +958,7 @@ static int kmer_table_build(smem_gpu_t* g, int k, const char* who) {
         (void)hipFree(g->d_kt);
         g->d_kt = nullptr;
         g->kt_k = g->kt_d = 0;
+        g->kt_min_next = 0;
         std::memset(g->kt_min, 0, sizeof(g->kt_min));
     }
     if (k == 0) return SMEM_OK;
@@ -958,7 +972,11 @@ static int kmer_table_build(smem_gpu_t* g, int k, const char* who) {
     unsigned long long mn[16] = {0};
     if (e == hipSuccess) e = smem_launch_kmer_table(g->d_occ64, g->primary, g->L2, k, p, nullptr);
     if (e == hipSuccess) e = smem_launch_kmer_min(p, k, d_mn, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(mn, d_mn, sizeof(unsigned long long) * (size_t)(k + 1), hipMemcpyDeviceToHost);
+    // level k + 1 is reduced from level k without being stored (mn[k + 1]; k = 15: no room, not reduced)
+    const bool next = k <= 14;
+    if (e == hipSuccess && next) e = smem_launch_kmer_min_next(g->d_occ64, g->primary, g->L2, p, k, d_mn + k + 1, nullptr);
+    if (e == hipSuccess)
+        e = hipMemcpy(mn, d_mn, sizeof(unsigned long long) * (size_t)(k + 1 + next), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (d_mn) (void)hipFree(d_mn);
     if (e != hipSuccess) {
@@ -968,11 +986,16 @@ static int kmer_table_build(smem_gpu_t* g, int k, const char* who) {
     g->d_kt = p;
     g->kt_k = k;
     for (int l = 1; l <= k; ++l) g->kt_min[l] = mn[l];
+    g->kt_min_next = next ? mn[k + 1] : 0;
     g->kt_d = smem_kmer_depth(g->kt_min, k);
     g->kt_build_s = now_s() - t0;
     if (getenv("SMEM_GPU_TIMES"))
-        fprintf(stderr, "[smem_gpu] k-mer table: k %d, %.1f MB, D %d, minsz[D] %llu, built in %.3f s\n", k,
-                n * 16.0 / 1e6, g->kt_d, (unsigned long long)g->kt_min[g->kt_d], g->kt_build_s);
+        fprintf(stderr,
+                "[smem_gpu] k-mer table: k %d, %.1f MB, D %d, minsz[D] %llu, minsz[k] %llu, unstored level %d min %llu, "
+                "probe depth %d (min_intv 1), built in %.3f s\n",
+                k, n * 16.0 / 1e6, g->kt_d, (unsigned long long)g->kt_min[g->kt_d], (unsigned long long)g->kt_min[k],
+                k + 1, (unsigned long long)g->kt_min_next, smem_kmer_probe_depth(g->kt_min, k, g->kt_min_next, 1),
+                g->kt_build_s);
     return SMEM_OK;
 }
 
@@ -993,6 +1016,13 @@ int smem_gpu_kmer_facts(smem_gpu_t* g, int* k, int* depth, uint64_t* minsz, int 
     if (depth) *depth = g->kt_d;
     for (int l = 0; minsz && l < n_minsz; ++l) minsz[l] = l < 16 ? g->kt_min[l] : 0;
     return SMEM_OK;
+}
+
+int smem_gpu_kmer_probe_depth(smem_gpu_t* g, int64_t min_intv, uint64_t* min_next) {
+    if (!g) return SMEM_E_ARG;
+    gpu_wait(g);
+    if (min_next) *min_next = g->kt_min_next;
+    return g->d_kt ? smem_kmer_probe_depth(g->kt_min, g->kt_k, g->kt_min_next, min_intv) : 0;
 }
 
 int smem_gpu_set_intv_cap(smem_gpu_t* g, int cap_per_read) {
@@ -1214,8 +1244,10 @@ static void fill_params(smem_batch_t* b, const smem_opt_t* o, smem::SeedParams& 
     P.start_width = o->start_width;
     // the depth below which the default kernel keeps a call's entries virtual: a re-seeding call's min_intv
     // is its match's size + 1, at most split_width + 1 (software/bwamem.c:272-276)
-    P.kt_dp0 = smem_kmer_call_depth(b->g->kt_min, b->g->kt_d, o->start_width);
-    P.kt_dp1 = smem_kmer_call_depth(b->g->kt_min, b->g->kt_d, (int64_t)std::max(o->split_width, 0) + 1);
+    // (smem_kmer_probe_depth: up to the table's deepest level where the unstored level after it is complete)
+    P.kt_dp0 = smem_kmer_probe_depth(b->g->kt_min, b->g->kt_k, b->g->kt_min_next, o->start_width);
+    P.kt_dp1 = smem_kmer_probe_depth(b->g->kt_min, b->g->kt_k, b->g->kt_min_next,
+                                     (int64_t)std::max(o->split_width, 0) + 1);
     P.scratch = b->d_scratch.p;
     P.cap_list = b->cap_list;
     const char* dbg = getenv("SMEM_DEBUG_FLAGS");

@@ -51,7 +51,7 @@ struct SeedParams {
     const uint4* kt;           // k-mer bi-interval table (smem_launch_kmer_table; variant 23), nullptr: none
     int kt_k;                  // its longest k-mer
     int kt_dp0, kt_dp1;        // seed_wp_kernel SKIP: the probe depth of calls with min_intv = start_width and of
-                               // re-seeding calls (min_intv <= split_width + 1): smem_kmer_call_depth, < kt_k; 0: none
+                               // re-seeding calls (min_intv <= split_width + 1): smem_kmer_probe_depth, <= kt_k; 0: none
 };
 
 // bwt_sa over the seeding output (software/bwamem.c:462-474, software/bwt.c:104-114)
@@ -104,6 +104,10 @@ hipError_t smem_launch_kmer_table(const uint32_t* occ64, uint64_t primary, const
                                   hipStream_t st);
 // mn[L] = the smallest x2 of table level L, L = 1..k (mn: k + 1 device words)
 hipError_t smem_launch_kmer_min(const uint4* kt, int k, unsigned long long* mn, hipStream_t st);
+// *mn_next = the smallest size among the strings of k + 1 bases (0: one is absent), computed from level k
+// and the index without storing the level (k <= 14; one device word)
+hipError_t smem_launch_kmer_min_next(const uint32_t* occ64, uint64_t primary, const uint64_t* L2, const uint4* kt, int k,
+                                     unsigned long long* mn_next, hipStream_t st);
 hipError_t smem_launch_finalize(const smem::FinalizeParams* F, int write, hipStream_t st);
 hipError_t smem_launch_fill_i32(int32_t* p, int32_t v, int n, hipStream_t st);
 hipError_t smem_launch_pack_intv(const smem::Intv* in, uint64_t n, uint4* out, hipStream_t st);

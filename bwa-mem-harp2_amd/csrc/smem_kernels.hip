@@ -379,8 +379,9 @@ __device__ __forceinline__ void wave_lds_fence() {
 // out: sel4's compare chain, which compiles to a branch tree), 128 the query byte by one bit test and
 // a 64-bit shift (out: qsel's compare chain, a branch tree again)
 // SKIP (with KT; DESIGN.md §5 "Virtual short entries"): the entries of a call whose strings are shorter
-// than dp bases are not stored and not extended.  With D the largest level below the table's depth at
-// which every string of D + 1 bases occurs and minsz[L] the smallest interval size of level L, dp is a
+// than dp bases are not stored and not extended.  With D the largest level up to the table's depth at
+// which every string of D + 1 bases occurs (level depth + 1 is not stored: the build reduces it on the
+// fly, kmer_next_level_min_kernel) and minsz[L] the smallest interval size of level L, dp is a
 // level <= D with minsz[dp] >= min_intv: the host passes one for a read's first calls (P.kt_dp0) and one
 // for its re-seeding calls (P.kt_dp1; smem_gpu.cpp fill_params).  Up to dp bases every forward extend
 // changes the size and none falls below min_intv, so a call starts with one probe of its first
@@ -401,9 +402,10 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
     constexpr uint32_t PR = PAIR ? 2u : 1u;  // entries per worker lane
     const int K = KT && P.kt ? P.kt_k : 0;
     // SKIP: the probe depth of a read's first calls (min_intv = start_width) and of its re-seeding calls
-    // (min_intv <= split_width + 1), chosen on the host (smem_kmer_call_depth); both below the table's depth
-    const uint32_t DP0 = SKIP && K > 0 && P.kt_dp0 < K ? (uint32_t)P.kt_dp0 : 0u;
-    const uint32_t DP1 = SKIP && K > 0 && P.kt_dp1 < K ? (uint32_t)P.kt_dp1 : 0u;
+    // (min_intv <= split_width + 1), chosen on the host (smem_kmer_probe_depth); at most the table's depth K
+    // (dp == K: the table's deepest level is probed, and kc, which holds K bases, is read whole)
+    const uint32_t DP0 = SKIP && K > 0 && P.kt_dp0 <= K ? (uint32_t)P.kt_dp0 : 0u;
+    const uint32_t DP1 = SKIP && K > 0 && P.kt_dp1 <= K ? (uint32_t)P.kt_dp1 : 0u;
     static_assert(OWN >= 1 && OWN <= 64 && NL >= 2 && NL < 32, "owners per wave / list entries");
     __shared__ WpWave<OWN, NL, PAIR, DPOS> wlds[4];
     WpWave<OWN, NL, PAIR, DPOS>* L = &wlds[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
@@ -1536,6 +1538,41 @@ __global__ __launch_bounds__(256) void kmer_level_min_kernel(const uint4* __rest
     if ((threadIdx.x & 63) == 0) atomicMin(mn + L, m);
 }
 
+// the same for level L + 1, which the table does not store: each thread extends the L-mers W of a strided
+// share backward by each base (as kmer_table_kernel does for a stored level; an absent W contributes 0)
+// and keeps the smallest size, nothing is written but the wave's one atomic into *mn_next (preset to ~0)
+__global__ __launch_bounds__(256) void kmer_next_level_min_kernel(SeedParams P, const uint4* __restrict__ kt, int L,
+                                                                  unsigned long long* __restrict__ mn_next) {
+    const uint64_t n = 1ull << (2 * L);
+    const uint4* lev = kt + (n - 4) / 3;
+    const uint4* o = reinterpret_cast<const uint4*>(P.occ64);  // block b: o[2b] counts, o[2b + 1] symbols
+    unsigned long long m = ~0ull;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += (uint64_t)gridDim.x * blockDim.x) {
+        const uint4 e = lev[w];
+        const uint64_t a = p_x0(e), b = p_x1(e), s = p_x2(e);
+        if (s == 0) {
+            m = 0;
+            continue;
+        }
+        const uint64_t k = a - 1, l = k + s;
+        uint64_t kk = k - (k >= P.primary), ll = l - (l >= P.primary);
+        if (kk >= P.L2[4]) kk = 0;  // (only a broken table: the loads stay inside the index)
+        if (ll >= P.L2[4]) ll = 0;
+        const Bucket32 vk{o[2 * (kk >> 6)], o[2 * (kk >> 6) + 1]}, vl{o[2 * (ll >> 6)], o[2 * (ll >> 6) + 1]};
+        for (int c = 0; c < 4; ++c) {
+            uint64_t na, nb, ns;
+            extend_counts64<false>(P, a, b, s, c, kk, ll, vk, vl, na, nb, ns);
+            m = ns < m ? ns : m;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long t = __shfl_xor(m, d, 64);
+        m = t < m ? t : m;
+    }
+    if ((threadIdx.x & 63) == 0) atomicMin(mn_next, m);
+}
+
 // Occ64 -> Occ192 (see rank192); one thread per 64-B line of 192 symbols
 __global__ __launch_bounds__(256) void occ192_kernel(const uint32_t* __restrict__ occ64, uint64_t n_blocks,
                                                       uint64_t n_lines, uint32_t* __restrict__ out) {
@@ -1599,6 +1636,22 @@ extern "C" hipError_t smem_launch_kmer_min(const uint4* kt, int k, unsigned long
         e = hipGetLastError();
     }
     return e;
+}
+
+extern "C" hipError_t smem_launch_kmer_min_next(const uint32_t* occ64, uint64_t primary, const uint64_t* L2, const uint4* kt,
+                                                 int k, unsigned long long* mn_next, hipStream_t st) {
+    if (k < 1 || k > 14) return hipErrorInvalidValue;
+    smem::SeedParams P;
+    memset(&P, 0, sizeof(P));
+    P.occ64 = occ64;
+    P.primary = primary;
+    for (int c = 0; c < 5; ++c) P.L2[c] = L2[c];
+    hipError_t e = hipMemsetAsync(mn_next, 0xFF, sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+    const uint64_t n = 1ull << (2 * k);
+    const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 16384);
+    hipLaunchKernelGGL(smem::kmer_next_level_min_kernel, dim3(grid), dim3(256), 0, st, P, kt, k, mn_next);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t smem_launch_occ192(const uint32_t* occ64, uint64_t n_blocks, uint32_t* out, hipStream_t st) {

@@ -27,6 +27,7 @@ EXPORTED = [
     "smem_batch_run", "smem_batch_fetch", "smem_batch_read", "smem_batch_results", "smem_batch_stats",
     "smem_gpu_set_lanes_per_cu", "smem_gpu_set_intv_cap", "smem_gpu_set_kernel_variant", "smem_gpu_get_kernel_variant", "smem_gpu_grid_reads", "smem_gpu_set_kmer_table", "smem_batch_debug", "smem_strerror",
     "smem_gpu_kmer_facts", "smem_gpu_seed_kernel", "smem_kmer_depth", "smem_kmer_call_depth",
+    "smem_kmer_probe_depth", "smem_gpu_kmer_probe_depth",
     "smem_gpu_build_id",
     "smem_bwt_build_sa", "smem_bwt_build_gpu_sa", "smem_sa_read", "smem_sa_write", "smem_sa_free", "smem_gpu_load_sa",
     "smem_batch_sa", "smem_batch_sa_results",
@@ -291,6 +292,11 @@ def load() -> C.CDLL:
         lib.smem_kmer_depth.restype = C.c_int
         lib.smem_kmer_call_depth.argtypes = [C.c_void_p, C.c_int, C.c_int64]
         lib.smem_kmer_call_depth.restype = C.c_int
+    if hasattr(lib, "smem_kmer_probe_depth"):  # absent from A/B libraries built before the unstored level's minimum
+        lib.smem_kmer_probe_depth.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int64]
+        lib.smem_kmer_probe_depth.restype = C.c_int
+        lib.smem_gpu_kmer_probe_depth.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_uint64)]
+        lib.smem_gpu_kmer_probe_depth.restype = C.c_int
     if hasattr(lib, "smem_batch_debug"):  # absent from older A/B builds
         lib.smem_batch_debug.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     lib.smem_strerror.argtypes = [C.c_int]
@@ -592,11 +598,24 @@ class Gpu:
 
     def kmer_facts(self) -> dict:
         """The k-mer table's facts (smem_gpu_kmer_facts): k its depth (0: none), D the largest level
-        such that every string of D + 1 bases occurs, minsz[L] the smallest interval size of level L."""
+        below k such that every string of D + 1 bases occurs, minsz[L] the smallest interval size of
+        level L (the stored levels only: see kmer_probe_depth for the depth a launch runs at)."""
         k, d = C.c_int(0), C.c_int(0)
         mn = np.zeros(16, dtype=np.uint64)
         _check(load().smem_gpu_kmer_facts(self._h, C.byref(k), C.byref(d), mn.ctypes.data, 16), "smem_gpu_kmer_facts")
         return {"k": k.value, "D": d.value, "minsz": [int(v) for v in mn[:k.value + 1]]}
+
+    def kmer_probe_depth(self, min_intv: int = 1) -> dict:
+        """The depth a launch probes the table at for calls with this min_intv, and the smallest size of
+        the unstored level k + 1 (smem_gpu_kmer_probe_depth).  kmer_facts()["D"] counts the stored levels
+        only (D <= k - 1); the kernel may also rely on level k + 1, which the build reduced without
+        storing it, so the depth here is k where kmer_facts would say k - 1.  A run takes it for
+        min_intv = start_width (a read's first calls) and split_width + 1 (its re-seeding calls)."""
+        nx = C.c_uint64(0)
+        dp = load().smem_gpu_kmer_probe_depth(self._h, int(min_intv), C.byref(nx))
+        if dp < 0:
+            _check(dp, "smem_gpu_kmer_probe_depth")
+        return {"depth": dp, "min_next": int(nx.value)}
 
     @property
     def seed_kernel(self) -> int:

@@ -680,7 +680,8 @@ int  smem_gpu_set_kmer_table(smem_gpu_t *gpu, int k);
  * bases (0: one is absent; L = 1..k, n_minsz words written), *depth the
  * largest level D < k such that every string of D + 1 bases occurs.  A
  * bwt_smem1 call skips the extends of strings of fewer than
- * smem_kmer_call_depth(minsz, D, min_intv) bases, min_intv taken as
+ * smem_kmer_probe_depth(minsz, k, min_next, min_intv) bases (below: D, or k
+ * where the unstored level k + 1 is complete too), min_intv taken as
  * start_width for a read's first calls and as split_width + 1 (the most a
  * re-seeding call can ask for) for its re-seeding calls. */
 int  smem_gpu_kmer_facts(smem_gpu_t *gpu, int *k, int *depth, uint64_t *minsz, int n_minsz);
@@ -688,6 +689,24 @@ int  smem_gpu_kmer_facts(smem_gpu_t *gpu, int *k, int *depth, uint64_t *minsz, i
  * sizes mn[1..k] (mn[0] unused) */
 int  smem_kmer_depth(const uint64_t *mn, int k);
 int  smem_kmer_call_depth(const uint64_t *mn, int depth, int64_t min_intv);
+/* The depth a launch really probes at.  *depth above stops at k - 1 because
+ * level D + 1 has to be seen complete, and smem_gpu_kmer_facts only reports
+ * the stored levels.  The build also reduces level k + 1, computed from level
+ * k and the index and never stored, to its smallest size (min_next; 0 or
+ * UINT64_MAX: a string of k + 1 bases is absent, or the level was not
+ * reduced, which is the case for k = 15).  smem_kmer_probe_depth is the
+ * largest level L <= k with levels 1 .. L + 1 all complete and
+ * mn[L] >= min_intv (min_intv < 1 taken as 1): k itself where all k levels
+ * and the unstored one are complete, and
+ * smem_kmer_call_depth(mn, smem_kmer_depth(mn, k), min_intv) otherwise.  So
+ * the reported D and the kernel's depth may differ by one: D counts the
+ * levels the table stores, the kernel may also rely on the one reduced beside
+ * them.  smem_gpu_kmer_probe_depth returns that depth for the handle's table
+ * (0: no table) and writes the unstored level's minimum to *min_next (may be
+ * NULL); a batch run passes it for min_intv = start_width and for
+ * split_width + 1. */
+int  smem_kmer_probe_depth(const uint64_t *mn, int k, uint64_t min_next, int64_t min_intv);
+int  smem_gpu_kmer_probe_depth(smem_gpu_t *gpu, int64_t min_intv, uint64_t *min_next);
 /* variant 9 (stamped diagnostic build): copy the per-wave cycle split
  * {advance, fetch, compute, iterations, active lanes, t0, t1, 0} of the last
  * run; returns the number of words copied or a negative code */
