@@ -24,13 +24,18 @@
 // the run-length CIGAR is built in the column array's LDS (dead by then), MD
 // is walked twice (length, then bytes) and output space is claimed from two
 // cursors, which also give the sizes a too-small pool needs.
+//
+// g2a_prep_kernel (at the end) makes the tasks and the lane groups' lists on the
+// device, for the host-buffer call and the resident batch stage alike; the
+// lists' lengths stay in device memory, a region that defers appends itself to
+// the scratch tier's list, and with a contig table the serial end also names
+// the contig of the final position (bns_pos2rid, software/bwamem.c:1548).
 #include "global_kernels.h"
 
 namespace smem {
 namespace {
 
 constexpr int MINUS_INF = -0x40000000;  // software/ksw.c:487
-constexpr int G2A_BADTRACE = 101;       // a guard tripped (never expected): the host reports SMEM_E_INTERNAL
 
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 
@@ -174,7 +179,14 @@ __device__ __forceinline__ void finish_region(const G2aParams& P, const G2aTask&
     Aln A;
     A.pos = -1, A.is_rev = 0, A.n_cigar = 0, A.NM = 0, A.score = 0, A.tries = 0, A.status = status;
     A.cigar_off = 0, A.md_off = 0, A.md_len = 0, A.pad = 0;
-    if (status == G2A_DEFERRED) atomicAdd(&P.cur[2], 1ull);
+    if (status == G2A_DEFERRED) {
+        // the scratch-tier launch redoes it: onto that launch's list, with the matrix it may need
+        atomicAdd(&P.cur[2], 1ull);
+        const uint32_t slot = atomicAdd(&P.cnt[G2A_N_BIG], 1u);
+        if (slot < P.defer_cap) P.defer[slot] = T.out;
+        atomicMax(&P.cur[3], (unsigned long long)g2a_scratch_need(qlen, tlen, P.mat[0], P.o_del, P.e_del, P.o_ins,
+                                                                  P.e_ins));
+    }
     if (status == G2A_OK) {
         // the CIGAR last op first, in the column array's LDS: at most 2 qlen + 1 runs
         uint32_t* rc = reinterpret_cast<uint32_t*>(eh);
@@ -238,6 +250,9 @@ __device__ __forceinline__ void finish_region(const G2aParams& P, const G2aTask&
             }
         }
     }
+    if (A.status == G2A_BADTRACE) atomicAdd(&P.cnt[G2A_N_BADTRACE], 1u);
+    // the contig of the final position (software/bwamem.c:1548)
+    if (P.rid) P.rid[T.out] = A.status == G2A_OK && P.ctg.off ? g2a_pos2rid(P.ctg.off, P.ctg.n, P.l_pac, A.pos) : -1;
     P.alns[T.out] = A;
 }
 
@@ -249,11 +264,13 @@ void g2a_kernel(G2aParams P) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDSB];
     __shared__ int8_t smat[32];
     const int lane = (int)threadIdx.x, lg = lane & (G - 1), grp = lane / G;
+    const uint32_t n = *P.n_dev;  // (the grid was sized from the host's upper bound)
+    if (blockIdx.x * NG >= n) return;
     if (lane == 0)
         for (int k = 0; k < 25; ++k) smat[k] = P.mat[k];
     __syncthreads();
     uint8_t* const mine = lds + grp * B;
-    for (uint32_t it = blockIdx.x * NG + grp; it < P.n; it += gridDim.x * NG) {
+    for (uint32_t it = blockIdx.x * NG + grp; it < n; it += gridDim.x * NG) {
         group_fence();
         const G2aTask T = P.task[P.list[it]];
         const int qlen = T.qlen, tlen = (int)(T.re - T.rb);
@@ -320,13 +337,121 @@ void g2a_kernel(G2aParams P) {
     }
 }
 
+// What the host loop of smem_reg2aln did per region, one lane per record: the record's read
+// (by bisection over rec_off, as fin_write_kernel finds it), the statuses that need no
+// alignment, the test at the head of bwa_fix_xref2 (software/bwa.c:195-199) when a contig
+// table is resident, else the task, its first band's shape and its lane-group class.  The
+// lists are filled a wave at a time: ballot, rank among the wave's lanes of the class, one
+// atomic per wave and class.
+__global__ __launch_bounds__(64) void g2a_prep_kernel(G2aPrepParams P) {
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    const int lane = (int)threadIdx.x;
+    int cls = -1;  // 0..2: 16 / 32 / 64 lanes, 3: scratch tier; -1: settled here
+    uint64_t big_need = 0;
+    if (k < P.n_rec) {
+        uint32_t lo = 0, hi = P.n_reads;  // the last r with rec_off[r] <= k
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (P.rec_off[mid] <= (uint64_t)k) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t r = lo;
+        Aln A;
+        A.pos = -1, A.is_rev = 0, A.n_cigar = 0, A.NM = 0, A.score = 0, A.tries = 0, A.status = G2A_OK;
+        A.cigar_off = 0, A.md_off = 0, A.md_len = 0, A.pad = 0;
+        uint64_t ri = k;
+        bool have = true;
+        if (P.idx) {
+            ri = P.idx[k];
+            if (P.reg_range && (ri < P.reg_range[r] || ri >= P.reg_range[r + 1])) {
+                have = false;  // the call is refused (SMEM_E_ARG): nothing is read through this index
+                atomicAdd(&P.cnt[G2A_N_BADIDX], 1u);
+                A.status = G2A_UNMAPPED;
+            }
+        }
+        if (have) {
+            const G2aReg* R = P.regs + ri;
+            const int64_t rb = R->rb, re = R->re;
+            const int qb = R->qb, qe = R->qe;
+            const int64_t l_query = (int64_t)(P.offs[r + 1] - P.offs[r]);
+            if (rb < 0 || re < 0) {  // software/bwamem.c:1489
+                A.status = G2A_UNMAPPED;
+            } else if (qb < 0 || (int64_t)qe > l_query) {  // (the host-buffer call refuses these before the launch)
+                A.status = G2A_BADTRACE;
+                atomicAdd(&P.cnt[G2A_N_BADTRACE], 1u);
+            } else if (qe <= qb || rb >= re || (rb < P.l_pac && re > P.l_pac) || re > 2 * P.l_pac) {
+                A.status = G2A_NOCIGAR, A.NM = -1, A.tries = 1;  // bwa_gen_cigar2 returns 0 (software/bwa.c:106-108)
+            } else {
+                bool xref = false;
+                if (P.ctg.off) {
+                    // the head of bwa_fix_xref2: the contig of the region's middle on the forward
+                    // strand, its ends on the mapping strand
+                    const int64_t m = (rb + re) >> 1;
+                    const bool rev = m >= P.l_pac;
+                    const int64_t fm = rev ? (P.l_pac << 1) - 1 - m : m;  // bns_depos
+                    const int id = g2a_pos2rid(P.ctg.off, P.ctg.n, P.l_pac, fm);
+                    if (id >= 0) {
+                        const int64_t off = P.ctg.off[id], len = P.ctg.len[id];
+                        const int64_t cb = rev ? (P.l_pac << 1) - (off + len) : off, ce = cb + len;
+                        xref = cb > rb || ce < re;
+                    }
+                }
+                if (xref) {
+                    A.status = G2A_XREF;
+                    atomicAdd(&P.cnt[G2A_N_XREF], 1u);
+                } else if (qe - qb > G2A_MAX_QLEN || re - rb > (int64_t)G2A_MAX_TLEN) {
+                    A.status = G2A_REJECT;
+                } else {
+                    G2aTask T;
+                    T.q_off = P.offs[r] + (uint64_t)qb, T.rb = rb, T.re = re, T.qlen = qe - qb, T.qb = qb;
+                    T.l_query = (int32_t)l_query, T.truesc = R->truesc, T.w = R->w, T.out = k;
+                    const int tlen = (int)(re - rb);
+                    const int w2 = g2a_first_w2(T.qlen, tlen, T.truesc, P.a, P.o_del, P.e_del, P.o_ins, P.e_ins, P.w, T.w);
+                    int n_col = 1;
+                    uint64_t need = (uint64_t)g2a_fixed_bytes(T.qlen, tlen);
+                    if (!(T.qlen == tlen && w2 == 0)) {
+                        const int w = g2a_band(T.qlen, tlen, P.a0, P.o_del, P.e_del, P.o_ins, P.e_ins, w2);
+                        n_col = T.qlen < 2 * w + 1 ? T.qlen : 2 * w + 1;
+                        need += (uint64_t)g2a_row_bytes(T.qlen, w) * (uint64_t)tlen;
+                    }
+                    cls = n_col <= 16 ? 0 : n_col <= 32 ? 1 : 2;
+                    while (cls < 3 && need > (uint64_t)g2a_group_lds(16 << cls)) ++cls;
+                    if (cls == 3) big_need = g2a_scratch_need(T.qlen, tlen, P.a0, P.o_del, P.e_del, P.o_ins, P.e_ins);
+                    P.task[k] = T;
+                }
+            }
+        }
+        // (a record with a task gets its alignment from the DP kernels)
+        if (cls < 0) P.alns[k] = A;
+        if (P.rid) P.rid[k] = -1;
+    }
+    const uint64_t below = (1ull << lane) - 1;
+    for (int c = 0; c < 4; ++c) {
+        const uint64_t m = __ballot(cls == c);
+        if (!m) continue;
+        uint32_t base = 0;
+        if (lane == __builtin_ctzll(m))
+            base = atomicAdd(&P.cnt[c == 3 ? G2A_N_BIG : G2A_N_LIST0 + c], (uint32_t)__builtin_popcountll(m));
+        base = __shfl(base, __builtin_ctzll(m));
+        if (cls == c) P.list[(uint64_t)c * P.n_rec + base + (uint32_t)__builtin_popcountll(m & below)] = k;
+    }
+    if (big_need) atomicMax(&P.cur[3], (unsigned long long)big_need);
+}
+
 }  // namespace
 }  // namespace smem
+
+extern "C" hipError_t smem_launch_g2a_prep(const smem::G2aPrepParams* P, hipStream_t st) {
+    if (P->n_rec == 0) return hipSuccess;
+    hipLaunchKernelGGL(smem::g2a_prep_kernel, dim3((P->n_rec + 63u) / 64u), dim3(64), 0, st, *P);
+    return hipGetLastError();
+}
 
 extern "C" hipError_t smem_launch_g2a(const smem::G2aParams* P, int group, hipStream_t st) {
     using namespace smem;
     if (P->n == 0) return hipSuccess;
-    const uint32_t per = 64u / (uint32_t)group, grid = (P->n + per - 1) / per;
+    const uint32_t per = 64u / (uint32_t)group, want = (P->n + per - 1) / per;
+    const uint32_t grid = want < (uint32_t)G2A_GRID_MAX ? want : (uint32_t)G2A_GRID_MAX;
     const dim3 g(grid), b(64);
     if (group == 16) hipLaunchKernelGGL((g2a_kernel<16, 4 * g2a_group_lds(16), false>), g, b, 0, st, *P);
     else if (group == 32) hipLaunchKernelGGL((g2a_kernel<32, 2 * g2a_group_lds(32), false>), g, b, 0, st, *P);

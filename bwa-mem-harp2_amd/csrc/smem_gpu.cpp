@@ -96,13 +96,13 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
 // the drain on the way out is what keeps that work from landing after the
 // caller resumed.  stage: upload (smem_batch_set_reads*), seed
 // (smem_batch_run), sa, chain, aln (smem_batch_chain2aln), fin (smem_reg_finalize,
-// smem_batch_reg_finalize), fetch, or any.
+// smem_batch_reg_finalize), g2a (smem_batch_reg2aln), fetch, or any.
 // ":sticky" also marks the device faulted, as a real runtime failure does;
 // ":hip=<code>" goes through fail() with that hipError_t, so the
 // classification decides (hip=9, hipErrorInvalidConfiguration: that call only;
 // hip=719, hipErrorLaunchFailure: the device).
-enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_N };
-const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin"};
+enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_G2A, ST_N };
+const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin", "g2a"};
 std::atomic<uint64_t> g_stage_calls[ST_N];
 
 int inject_fault(int stage) {
@@ -324,6 +324,12 @@ struct smem_gpu {
     int32_t* d_fin_subn = nullptr;
     std::mutex fin_mu;
     std::atomic<bool> fin_used{false};
+    // the contig table (smem_gpu_load_contigs): bns->anns[].offset / .len; ctg_l_pac: the l_pac it tiles
+    int64_t* d_ctg_off = nullptr;
+    int32_t* d_ctg_len = nullptr;
+    int n_ctg = 0;
+    int64_t ctg_l_pac = 0;
+    std::atomic<bool> g2a_used{false};  // as fin_used, for smem_batch_reg2aln's buffers
     int64_t l_pac = 0;
     uint64_t n_sa = 0;
     uint32_t sa_shift = 0;
@@ -446,6 +452,25 @@ struct FinBufs {
     }
 };
 
+// device buffers of regions -> alignments (csrc/global_kernels.h G2aPrepParams / G2aParams)
+struct G2aBufs {
+    DevBuf<smem::G2aTask> task;
+    DevBuf<uint32_t> list, cnt, cigar;
+    DevBuf<unsigned long long> cur;
+    DevBuf<smem::Aln> alns;
+    DevBuf<int32_t> rid;
+    DevBuf<char> md;
+    DevBuf<uint8_t> scratch;
+    DevBuf<uint64_t> idx, idx_off;  // the caller's selection
+    template <class F>
+    void each(F&& f) {
+        f(task); f(list); f(cnt); f(cigar); f(cur); f(alns); f(rid); f(md); f(scratch); f(idx); f(idx_off);
+    }
+    void release() {
+        each([](auto& x) { x.release(); });
+    }
+};
+
 struct smem_batch {
     smem_gpu_t* g = nullptr;
     char* arena_dev = nullptr;   // the blocks a reserved slot's buffers are carved from (Arena)
@@ -536,6 +561,17 @@ struct smem_batch {
     HostBuf<int32_t> h_fin_status;
     bool fin_ran = false, fin_fetched = false;
     uint64_t tot_fin = 0, tot_fin_sel = 0;
+    // alignments (smem_batch_reg2aln): nothing here is allocated until the stage is called
+    G2aBufs g2a;
+    HostBuf<uint64_t> h_g2a_idx;              // the caller's idx, then idx_off[n + 1] (pinned: the copy is asynchronous)
+    HostBuf<uint64_t> h_g2a_ctr;              // [0, 4) the u32 counters, [4, 8) the u64 cursors
+    HostBuf<uint64_t> h_g2a_off;              // aln_off[n + 1]
+    HostBuf<smem::Aln> h_g2a_alns;
+    HostBuf<int32_t> h_g2a_rid;
+    HostBuf<uint32_t> h_g2a_cigar;
+    HostBuf<char> h_g2a_md;
+    bool g2a_ran = false, g2a_fetched = false, g2a_own_idx = false;
+    uint64_t tot_g2a = 0, tot_g2a_cigar = 0, tot_g2a_md = 0;
     smem_batch_stats_t stats{};
 };
 
@@ -557,6 +593,8 @@ static void batch_bufs(smem_batch_t* b, D&& d, H&& h) {
     d(b->d_aln_out); d(b->d_aln_ctr); b->aln_heavy.each(d); h(b->h_aln_regoff); h(b->h_aln_regs);
     b->fin.each(d); h(b->h_fin_ids); h(b->h_fin_off); h(b->h_fin_idx); h(b->h_fin_regs); h(b->h_fin_sel);
     h(b->h_fin_status);
+    b->g2a.each(d); h(b->h_g2a_idx); h(b->h_g2a_ctr); h(b->h_g2a_off); h(b->h_g2a_alns); h(b->h_g2a_rid);
+    h(b->h_g2a_cigar); h(b->h_g2a_md);
     h(b->h_ctr); h(b->h_tot); h(b->h_intv); h(b->h_calls);
     d(b->d_pintv); h(b->h_pintv); h(b->h_intv_off); h(b->h_call_off);
 }
@@ -1092,6 +1130,8 @@ void smem_gpu_shutdown(smem_gpu_t* g) {
     if (g->d_pac) (void)hipFree(g->d_pac);
     if (g->d_fin_log) (void)hipFree(g->d_fin_log);
     if (g->d_fin_subn) (void)hipFree(g->d_fin_subn);
+    if (g->d_ctg_off) (void)hipFree(g->d_ctg_off);
+    if (g->d_ctg_len) (void)hipFree(g->d_ctg_len);
     for (auto& p : g->pairs) {
         (void)hipStreamDestroy(p.first);
         (void)hipStreamDestroy(p.second);
@@ -1264,7 +1304,7 @@ static int batch_run_impl(smem_batch_t* b, const smem_opt_t* opt) {
     b->chain_ran = b->chain_fetched = false;
     b->tot_chains = b->tot_seeds = 0;
     b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
     b->tot_regs = 0;
     b->stats = smem_batch_stats_t{};
     b->stats.block = 256;
@@ -1402,11 +1442,12 @@ static int fetch_impl(smem_batch_t* b, int mask) {
     BatchCall call(b);
     if (call.rc) return call.rc;
     // views of an earlier fetch end here (its buffers may be regrown below)
-    b->fetched = b->sa_fetched = b->chain_fetched = b->aln_fetched = b->fin_fetched = false;
+    b->fetched = b->sa_fetched = b->chain_fetched = b->aln_fetched = b->fin_fetched = b->g2a_fetched = false;
     const int n = b->n_reads;
     const bool f_intv = mask & SMEM_FETCH_INTV, f_sa = (mask & SMEM_FETCH_SA) && b->sa_ran;
     const bool f_chain = (mask & SMEM_FETCH_CHAINS) && b->chain_ran, f_aln = (mask & SMEM_FETCH_REGS) && b->aln_ran;
     const bool f_fin = (mask & SMEM_FETCH_FIN) && b->fin_ran;
+    const bool f_g2a = (mask & SMEM_FETCH_ALN) && b->g2a_ran;
     // pinned result buffers grow with headroom: a streamed batch whose next
     // chunk holds a few more intervals must not re-pin a gigabyte
     if (!f_intv) {
@@ -1488,9 +1529,33 @@ static int fetch_impl(smem_batch_t* b, int mask) {
             HIP_TRY(hipMemcpyAsync(b->h_fin_idx.p, b->fin.out_idx.p, sizeof(uint64_t) * b->tot_fin_sel,
                                    hipMemcpyDeviceToHost, b->st));
     }
+    if (f_g2a) {
+        HIP_TRY(b->h_g2a_off.grow((uint64_t)n + 1));
+        HIP_TRY(b->h_g2a_alns.grow(b->tot_g2a));
+        HIP_TRY(b->h_g2a_rid.grow(b->tot_g2a));
+        HIP_TRY(b->h_g2a_cigar.grow(b->tot_g2a_cigar));
+        HIP_TRY(b->h_g2a_md.grow(b->tot_g2a_md));
+        if (n > 0)
+            HIP_TRY(hipMemcpyAsync(b->h_g2a_off.p, b->g2a_own_idx ? b->g2a.idx_off.p : b->fin.sel_off.p,
+                                   sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, b->st));
+        else
+            b->h_g2a_off.p[0] = 0;
+        if (b->tot_g2a) {
+            HIP_TRY(hipMemcpyAsync(b->h_g2a_alns.p, b->g2a.alns.p, sizeof(smem::Aln) * b->tot_g2a, hipMemcpyDeviceToHost,
+                                   b->st));
+            HIP_TRY(hipMemcpyAsync(b->h_g2a_rid.p, b->g2a.rid.p, sizeof(int32_t) * b->tot_g2a, hipMemcpyDeviceToHost,
+                                   b->st));
+        }
+        if (b->tot_g2a_cigar)
+            HIP_TRY(hipMemcpyAsync(b->h_g2a_cigar.p, b->g2a.cigar.p, sizeof(uint32_t) * b->tot_g2a_cigar,
+                                   hipMemcpyDeviceToHost, b->st));
+        if (b->tot_g2a_md)
+            HIP_TRY(hipMemcpyAsync(b->h_g2a_md.p, b->g2a.md.p, b->tot_g2a_md, hipMemcpyDeviceToHost, b->st));
+    }
     INJECT(ST_FETCH);
     HIP_TRY(hipStreamSynchronize(b->st));
     b->fin_fetched = f_fin;
+    b->g2a_fetched = f_g2a;
     b->fetched = f_intv;
     b->sa_fetched = f_sa;
     b->chain_fetched = f_chain;
@@ -1507,9 +1572,10 @@ int smem_batch_fetch(smem_batch_t* b) {
 int smem_batch_fetch_mask(smem_batch_t* b, int mask) {
     g_err[0] = 0;
     if (!b || !b->ran) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: batch has not run");
-    if (mask & ~(SMEM_FETCH_ALL | SMEM_FETCH_FIN)) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: unknown bits");
+    if (mask & ~(SMEM_FETCH_ALL | SMEM_FETCH_FIN | SMEM_FETCH_ALN)) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: unknown bits");
     if (((mask & SMEM_FETCH_SA) && !b->sa_ran) || ((mask & SMEM_FETCH_CHAINS) && !b->chain_ran) ||
-        ((mask & SMEM_FETCH_REGS) && !b->aln_ran) || ((mask & SMEM_FETCH_FIN) && !b->fin_ran))
+        ((mask & SMEM_FETCH_REGS) && !b->aln_ran) || ((mask & SMEM_FETCH_FIN) && !b->fin_ran) ||
+        ((mask & SMEM_FETCH_ALN) && !b->g2a_ran))
         return fail(SMEM_E_ARG, "smem_batch_fetch_mask: a requested stage has not run on this batch");
     return fetch_impl(b, mask);
 }
@@ -1683,7 +1749,7 @@ int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
     if (call.rc) return call.rc;
     b->sa_ran = b->chain_ran = b->aln_ran = false;
     b->sa_fetched = b->chain_fetched = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
     // the densified SA may still be in the making (smem_gpu_load_sa runs it
     // in the background): until its event has passed, the walk goes to the
     // stored samples instead (the same positions, sa_intv / D times the LF
@@ -1750,7 +1816,7 @@ int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
     b->sa_min_seed_len = min_seed_len;
     b->chain_ran = b->chain_fetched = false;
     b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
     return SMEM_OK;
 }
 
@@ -1772,7 +1838,7 @@ int smem_batch_chain(smem_batch_t* b, int64_t l_pac, const smem_chain_opt_t* opt
     if (call.rc) return call.rc;
     b->chain_ran = b->aln_ran = false;
     b->chain_fetched = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
     const int n = b->n_reads;
     const uint64_t no = std::max<uint64_t>(b->tot_occ, 1);
     HIP_TRY(b->d_seed.grow(no));
@@ -1880,7 +1946,7 @@ int smem_batch_chain(smem_batch_t* b, int64_t l_pac, const smem_chain_opt_t* opt
     b->chain_fetched = false;
     b->chain_filtered = opt->filter != 0;
     b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
     return SMEM_OK;
 }
 
@@ -2578,7 +2644,7 @@ int smem_batch_chain2aln(smem_batch_t* b, const smem_aln_opt_t* opt) {
     BatchCall call(b, aln_two_streams());
     if (call.rc) return call.rc;
     b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
     const int n = b->n_reads;
     const uint64_t ns = std::max<uint64_t>(b->tot_seeds, 1);
     HIP_TRY(b->d_aln_srt.grow(ns + 1));
@@ -2821,7 +2887,82 @@ int smem_chain2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint6
 // ---- regions -> alignments (mem_reg2aln's alignment part, software/bwamem.c:1504-1547)
 static_assert(sizeof(smem_aln_t) == sizeof(smem::Aln), "alignment layout");
 static_assert(SMEM_ALN_UNMAPPED == smem::G2A_UNMAPPED && SMEM_ALN_NOCIGAR == smem::G2A_NOCIGAR &&
-              SMEM_ALN_REJECT == smem::G2A_REJECT, "alignment status values");
+              SMEM_ALN_REJECT == smem::G2A_REJECT && SMEM_ALN_XREF == smem::G2A_XREF, "alignment status values");
+static_assert(sizeof(smem_alnreg_t) == sizeof(smem::G2aReg), "region layout");
+
+// One pass of regions -> alignments, shared by smem_reg2aln and smem_batch_reg2aln: the caller
+// fills the buffers' pointers, run_g2a enqueues and waits.
+struct G2aPass {
+    smem::G2aPrepParams PP;
+    smem::G2aParams P;
+    uint32_t* h_cnt = nullptr;            // [G2A_CNTS], host (pinned in a batch)
+    unsigned long long* h_cur = nullptr;  // [4]
+    DevBuf<uint8_t>* scratch = nullptr;   // the scratch tier's slabs, grown here
+    hipEvent_t* ev = nullptr;             // 5 events
+    int inject = -1;                      // the SMEM_GPU_FAIL stage to inject once the work is enqueued; -1: none
+    float ms_prep = 0.f, ms_dp = 0.f;
+};
+
+static void g2a_pass_params(G2aPass& R, const smem_aln_opt_t* opt, int64_t l_pac) {
+    const smem_ksw_opt_t& sc = opt->sc;
+    std::memset(&R.PP, 0, sizeof(R.PP));
+    std::memset(&R.P, 0, sizeof(R.P));
+    R.PP.l_pac = R.P.l_pac = l_pac;
+    R.PP.a0 = sc.mat[0];
+    R.PP.o_del = R.P.o_del = sc.o_del, R.PP.e_del = R.P.e_del = sc.e_del;
+    R.PP.o_ins = R.P.o_ins = sc.o_ins, R.PP.e_ins = R.P.e_ins = sc.e_ins;
+    R.PP.a = R.P.a = opt->a, R.PP.w = R.P.w = opt->w;
+    std::memcpy(R.P.mat, sc.mat, 25);
+}
+
+// the prep kernel, the three lane-group launches over its lists (their lengths stay on the
+// device), the counters' readback -- the only thing the host reads inside a pass -- and the
+// scratch-tier launch over what the prep kernel classed there and what deferred
+static int run_g2a(G2aPass& R, hipStream_t st) {
+    const uint32_t n = R.PP.n_rec;
+    R.P.task = R.PP.task, R.P.alns = R.PP.alns, R.P.rid = R.PP.rid, R.P.ctg = R.PP.ctg;
+    R.P.cur = R.PP.cur, R.P.cnt = R.PP.cnt;
+    R.P.defer = R.PP.list + 3ull * n, R.P.defer_cap = n;
+    HIP_TRY(hipMemsetAsync(R.PP.cnt, 0, sizeof(uint32_t) * smem::G2A_CNTS, st));
+    HIP_TRY(hipMemsetAsync(R.PP.cur, 0, sizeof(unsigned long long) * 4, st));
+    HIP_TRY(hipEventRecord(R.ev[0], st));
+    HIP_TRY(smem_launch_g2a_prep(&R.PP, st));
+    HIP_TRY(hipEventRecord(R.ev[1], st));
+    for (int c = 0; c < 3; ++c) {
+        R.P.list = R.PP.list + (uint64_t)c * n, R.P.n_dev = R.PP.cnt + smem::G2A_N_LIST0 + c, R.P.n = n;
+        HIP_TRY(smem_launch_g2a(&R.P, 16 << c, st));
+    }
+    HIP_TRY(hipEventRecord(R.ev[2], st));
+    HIP_TRY(hipMemcpyAsync(R.h_cnt, R.PP.cnt, sizeof(uint32_t) * smem::G2A_CNTS, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(R.h_cur, R.PP.cur, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost, st));
+    if (R.inject >= 0) INJECT(R.inject);
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, R.ev[0], R.ev[1]));
+    R.ms_prep = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, R.ev[1], R.ev[2]));
+    R.ms_dp = ms;
+    if (R.h_cnt[smem::G2A_N_BADIDX]) return fail(SMEM_E_ARG, "regions -> alignments: an index outside its read's final regions");
+    const uint32_t n_big = R.h_cnt[smem::G2A_N_BIG];
+    if (n_big > n) return fail(SMEM_E_INTERNAL, "regions -> alignments: more deferred regions than records");
+    if (n_big) {  // no group's LDS holds them, or a retry's wider band outgrew it
+        const uint64_t stride = std::max<uint64_t>((R.h_cur[3] + 255) & ~255ull, 256);
+        uint64_t blocks = std::max<uint64_t>(smem::G2A_BIG_BLOCKS_MIN, smem::G2A_BIG_SCRATCH / stride);
+        blocks = std::min<uint64_t>(std::min<uint64_t>(blocks, smem::G2A_BIG_BLOCKS_MAX), n_big);
+        HIP_TRY(R.scratch->grow(blocks * stride + 256));
+        R.P.list = R.P.defer, R.P.n_dev = R.PP.cnt + smem::G2A_N_BIG, R.P.n = n_big;
+        R.P.scratch = R.scratch->p, R.P.scratch_stride = stride;
+        HIP_TRY(hipEventRecord(R.ev[3], st));
+        HIP_TRY(smem_launch_g2a_big(&R.P, (uint32_t)blocks, st));
+        HIP_TRY(hipEventRecord(R.ev[4], st));
+        HIP_TRY(hipMemcpyAsync(R.h_cnt, R.PP.cnt, sizeof(uint32_t) * smem::G2A_CNTS, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(R.h_cur, R.PP.cur, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipEventElapsedTime(&ms, R.ev[3], R.ev[4]));
+        R.ms_dp += ms;
+    }
+    return SMEM_OK;
+}
 
 int smem_reg2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_t* offs, const smem_alnreg_t* regs,
                  const uint64_t* reg_off, const uint8_t* pac, int64_t l_pac, const smem_aln_opt_t* opt,
@@ -2847,68 +2988,35 @@ int smem_reg2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_
     // query codes index the 25-entry scoring matrix: 0..4 only
     for (uint64_t k = offs[0]; k < n_bases; ++k)
         if (codes[k] > 4) return fail(SMEM_E_ARG, "smem_reg2aln: query code > 4");
-    // every region is settled here (unmapped, no CIGAR, outside the limits) or becomes a
-    // task whose shape the host has checked; tasks go to the lane-group size their first
-    // band asks for, or straight to the scratch-tier launch when no group's LDS holds them
-    const smem_ksw_opt_t& sc = opt->sc;
-    std::vector<smem::G2aTask> tasks;
-    std::vector<uint32_t> list[4];  // 16, 32, 64 lanes; scratch tier
-    tasks.reserve(n_regs);
+    // the host keeps the argument checks; settling the regions that need no alignment, the
+    // tasks and the lane-group lists are the prep kernel's (csrc/global_kernels.hip), which the
+    // batch stage shares
     for (int r = 0; r < n_reads; ++r) {
         const int64_t l_query = (int64_t)(offs[r + 1] - offs[r]);
         for (uint64_t k = reg_off[r]; k < reg_off[r + 1]; ++k) {
             const smem_alnreg_t& R = regs[k];
-            smem_aln_t& A = alns[k];
-            std::memset(&A, 0, sizeof(A));
-            A.pos = -1;
-            if (R.rb < 0 || R.re < 0) {  // software/bwamem.c:1489
-                A.status = SMEM_ALN_UNMAPPED;
-                continue;
-            }
+            if (R.rb < 0 || R.re < 0) continue;  // unmapped (software/bwamem.c:1489)
             if (R.qb < 0 || R.qe > l_query) return fail(SMEM_E_ARG, "smem_reg2aln: region outside its read");
-            // bwa_gen_cigar2 returns 0 (software/bwa.c:106-108)
-            if (R.qe <= R.qb || R.rb >= R.re || (R.rb < l_pac && R.re > l_pac) || R.re > 2 * l_pac) {
-                A.status = SMEM_ALN_NOCIGAR, A.NM = -1, A.tries = 1;
-                continue;
-            }
-            if (R.qe - R.qb > smem::G2A_MAX_QLEN || R.re - R.rb > smem::G2A_MAX_TLEN) {
-                A.status = SMEM_ALN_REJECT;
-                continue;
-            }
-            smem::G2aTask T;
-            T.q_off = offs[r] + (uint64_t)R.qb, T.rb = R.rb, T.re = R.re, T.qlen = R.qe - R.qb, T.qb = R.qb;
-            T.l_query = (int32_t)l_query, T.truesc = R.truesc, T.w = R.w, T.out = (uint32_t)k;
-            const int tlen = (int)(R.re - R.rb);
-            const int w2 = smem::g2a_first_w2(T.qlen, tlen, R.truesc, opt->a, sc.o_del, sc.e_del, sc.o_ins, sc.e_ins,
-                                              opt->w, R.w);
-            int n_col = 1;
-            uint64_t need = (uint64_t)smem::g2a_fixed_bytes(T.qlen, tlen);
-            if (!(T.qlen == tlen && w2 == 0)) {
-                const int w = smem::g2a_band(T.qlen, tlen, sc.mat[0], sc.o_del, sc.e_del, sc.o_ins, sc.e_ins, w2);
-                n_col = std::min(T.qlen, 2 * w + 1);
-                need += (uint64_t)smem::g2a_row_bytes(T.qlen, w) * tlen;
-            }
-            int cls = n_col <= 16 ? 0 : n_col <= 32 ? 1 : 2;
-            while (cls < 3 && need > (uint64_t)smem::g2a_group_lds(16 << cls)) ++cls;
-            list[cls].push_back((uint32_t)tasks.size());
-            tasks.push_back(T);
         }
     }
-    const uint64_t n_tasks = tasks.size();
-    if (n_tasks == 0) return SMEM_OK;
+    const uint64_t r0 = reg_off[0], n_rec = n_regs - r0;  // (regions before the first read's are nobody's)
+    if (n_rec == 0) return SMEM_OK;
     DevBuf<uint8_t> dcodes, dpac, dscratch;
+    DevBuf<smem::G2aReg> dregs;
+    DevBuf<uint64_t> doffs, dregoff;
     DevBuf<smem::G2aTask> dtask;
-    DevBuf<uint32_t> dlist, dcig;
+    DevBuf<uint32_t> dlist, dcig, dcnt;
     DevBuf<smem::Aln> daln;
     DevBuf<char> dmd;
     DevBuf<unsigned long long> dcur;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<uint64_t> off0;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     struct Guard {
         std::function<void()> f;
         ~Guard() { f(); }
     } guard{[&] {
-        dcodes.release(); dpac.release(); dscratch.release(); dtask.release(); dlist.release(); dcig.release();
-        daln.release(); dmd.release(); dcur.release();
+        dcodes.release(); dpac.release(); dscratch.release(); dregs.release(); doffs.release(); dregoff.release();
+        dtask.release(); dlist.release(); dcig.release(); dcnt.release(); daln.release(); dmd.release(); dcur.release();
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }};
@@ -2919,77 +3027,46 @@ int smem_reg2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_
     const uint64_t pac_bytes = (uint64_t)(l_pac + 3) / 4;
     HIP_TRY(dcodes.ensure(n_bases + 64));
     if (pac) HIP_TRY(dpac.ensure(pac_bytes + 64));
-    HIP_TRY(dtask.ensure(n_tasks));
-    HIP_TRY(dlist.ensure(2 * n_tasks));  // the three group lists, then room for the deferred ones
-    HIP_TRY(daln.ensure(n_regs));
+    HIP_TRY(dregs.ensure(n_rec));
+    HIP_TRY(doffs.ensure((uint64_t)n_reads + 1));
+    HIP_TRY(dregoff.ensure((uint64_t)n_reads + 1));
+    HIP_TRY(dtask.ensure(n_rec));
+    HIP_TRY(dlist.ensure(4 * n_rec));  // the three group lists, the scratch tier's
+    HIP_TRY(dcnt.ensure(smem::G2A_CNTS));
+    HIP_TRY(daln.ensure(n_rec));
     HIP_TRY(dcig.ensure(cigar_cap));
     HIP_TRY(dmd.ensure(md_cap));
     HIP_TRY(dcur.ensure(4));
+    const uint64_t* h_off = reg_off;
+    if (r0) {  // the kernels index regs from 0
+        off0.resize((size_t)n_reads + 1);
+        for (int r = 0; r <= n_reads; ++r) off0[(size_t)r] = reg_off[r] - r0;
+        h_off = off0.data();
+    }
     if (n_bases) HIP_TRY(hipMemcpyAsync(dcodes.p, codes, n_bases, hipMemcpyHostToDevice, st));
     if (pac) HIP_TRY(hipMemcpyAsync(dpac.p, pac, pac_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dtask.p, tasks.data(), sizeof(smem::G2aTask) * n_tasks, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(dcur.p, 0, 4 * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(daln.p, 0, sizeof(smem::Aln) * n_regs, st));
-    smem::G2aParams P;
-    std::memset(&P, 0, sizeof(P));
-    P.task = dtask.p, P.codes = dcodes.p, P.pac = pac ? dpac.p : g->d_pac, P.l_pac = l_pac;
-    std::memcpy(P.mat, sc.mat, 25);
-    P.o_del = sc.o_del, P.e_del = sc.e_del, P.o_ins = sc.o_ins, P.e_ins = sc.e_ins, P.a = opt->a, P.w = opt->w;
-    P.alns = daln.p, P.cigar = dcig.p, P.md = dmd.p, P.cigar_cap = cigar_cap, P.md_cap = md_cap, P.cur = dcur.p;
-    uint64_t at = 0;
-    HIP_TRY(hipEventRecord(ev[0], st));
-    for (int c = 0; c < 3; ++c) {
-        if (list[c].empty()) continue;
-        HIP_TRY(hipMemcpyAsync(dlist.p + at, list[c].data(), 4 * list[c].size(), hipMemcpyHostToDevice, st));
-        P.list = dlist.p + at, P.n = (uint32_t)list[c].size();
-        HIP_TRY(smem_launch_g2a(&P, 16 << c, st));
-        at += list[c].size();
-    }
-    HIP_TRY(hipEventRecord(ev[1], st));
-    unsigned long long cur[4] = {0, 0, 0, 0};
-    std::vector<smem::Aln> got(n_regs);
-    HIP_TRY(hipMemcpyAsync(cur, dcur.p, sizeof(cur), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(got.data(), daln.p, sizeof(smem::Aln) * n_regs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(dregs.p, regs + r0, sizeof(smem::G2aReg) * n_rec, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(doffs.p, offs, 8 * ((size_t)n_reads + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dregoff.p, h_off, 8 * ((size_t)n_reads + 1), hipMemcpyHostToDevice, st));
+    uint32_t h_cnt[smem::G2A_CNTS] = {0};
+    unsigned long long h_cur[4] = {0, 0, 0, 0};
+    G2aPass R;
+    g2a_pass_params(R, opt, l_pac);
+    R.PP.regs = dregs.p, R.PP.rec_off = dregoff.p, R.PP.offs = doffs.p;
+    R.PP.n_reads = (uint32_t)n_reads, R.PP.n_rec = (uint32_t)n_rec;
+    R.PP.task = dtask.p, R.PP.list = dlist.p, R.PP.cnt = dcnt.p, R.PP.cur = dcur.p, R.PP.alns = daln.p;
+    R.P.codes = dcodes.p, R.P.pac = pac ? dpac.p : g->d_pac;
+    R.P.cigar = dcig.p, R.P.md = dmd.p, R.P.cigar_cap = cigar_cap, R.P.md_cap = md_cap;
+    R.h_cnt = h_cnt, R.h_cur = h_cur, R.scratch = &dscratch, R.ev = ev;
+    if (int rc = run_g2a(R, st)) return rc;
+    if (kernel_ms) *kernel_ms = (double)R.ms_dp;
+    if (h_cnt[smem::G2A_N_BADTRACE]) return fail(SMEM_E_INTERNAL, "smem_reg2aln: a region's traceback left its band");
+    HIP_TRY(hipMemcpyAsync(alns + r0, daln.p, sizeof(smem::Aln) * n_rec, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f, ms2 = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    // a retry's wider band outgrew its group's LDS: those regions again, with the scratch tier
-    if (cur[2])
-        for (uint64_t k = 0; k < n_tasks; ++k)
-            if (got[tasks[k].out].status == smem::G2A_DEFERRED) list[3].push_back((uint32_t)k);
-    if (!list[3].empty()) {
-        uint64_t stride = 0;
-        for (uint32_t k : list[3]) {
-            const smem::G2aTask& T = tasks[k];
-            const int tlen = (int)(T.re - T.rb);
-            const int w = smem::g2a_band(T.qlen, tlen, sc.mat[0], sc.o_del, sc.e_del, sc.o_ins, sc.e_ins, INT32_MAX);
-            stride = std::max<uint64_t>(stride, (uint64_t)smem::g2a_row_bytes(T.qlen, w) * tlen);
-        }
-        stride = std::max<uint64_t>((stride + 255) & ~255ull, 256);
-        uint64_t blocks = std::max<uint64_t>(smem::G2A_BIG_BLOCKS_MIN, smem::G2A_BIG_SCRATCH / stride);
-        blocks = std::min<uint64_t>(std::min<uint64_t>(blocks, smem::G2A_BIG_BLOCKS_MAX), list[3].size());
-        HIP_TRY(dscratch.ensure(blocks * stride + 256));
-        HIP_TRY(hipMemcpyAsync(dlist.p + at, list[3].data(), 4 * list[3].size(), hipMemcpyHostToDevice, st));
-        P.list = dlist.p + at, P.n = (uint32_t)list[3].size();
-        P.scratch = dscratch.p, P.scratch_stride = stride;
-        HIP_TRY(hipEventRecord(ev[2], st));
-        HIP_TRY(smem_launch_g2a_big(&P, (uint32_t)blocks, st));
-        HIP_TRY(hipEventRecord(ev[3], st));
-        HIP_TRY(hipMemcpyAsync(cur, dcur.p, sizeof(cur), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(got.data(), daln.p, sizeof(smem::Aln) * n_regs, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipEventElapsedTime(&ms2, ev[2], ev[3]));
-    }
-    if (kernel_ms) *kernel_ms = (double)ms + (double)ms2;
-    for (uint64_t k = 0; k < n_tasks; ++k) {
-        const smem::Aln& A = got[tasks[k].out];
-        if (A.status != smem::G2A_OK) return fail(SMEM_E_INTERNAL, "smem_reg2aln: a region's traceback left its band");
-        std::memcpy(&alns[tasks[k].out], &A, sizeof(A));
-    }
-    *n_cigar_words = cur[0], *n_md_bytes = cur[1];
-    if (cur[0] > cigar_cap || cur[1] > md_cap) return fail(SMEM_E_CAPACITY, "smem_reg2aln: cigar / md pool too small");
-    if (cur[0]) HIP_TRY(hipMemcpyAsync(cigar, dcig.p, 4 * cur[0], hipMemcpyDeviceToHost, st));
-    if (cur[1]) HIP_TRY(hipMemcpyAsync(md, dmd.p, cur[1], hipMemcpyDeviceToHost, st));
+    *n_cigar_words = h_cur[0], *n_md_bytes = h_cur[1];
+    if (h_cur[0] > cigar_cap || h_cur[1] > md_cap) return fail(SMEM_E_CAPACITY, "smem_reg2aln: cigar / md pool too small");
+    if (h_cur[0]) HIP_TRY(hipMemcpyAsync(cigar, dcig.p, 4 * h_cur[0], hipMemcpyDeviceToHost, st));
+    if (h_cur[1]) HIP_TRY(hipMemcpyAsync(md, dmd.p, h_cur[1], hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return SMEM_OK;
 }
@@ -3193,7 +3270,7 @@ int smem_batch_reg_finalize(smem_batch_t* b, const int64_t* ids, int64_t id0, co
     smem_gpu_t* g = b->g;
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->fin_ran = b->fin_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
     g->fin_used.store(true);  // slots reserved from now on carry the stage's buffers
     const int n = b->n_reads;
     if (int rc = fin_tables(g)) return rc;
@@ -3243,6 +3320,178 @@ int smem_batch_fin_results(const smem_batch_t* b, const smem_alnreg_t** regs_out
     if (status) *status = b->h_fin_status.p;
     if (n_out) *n_out = b->tot_fin;
     if (n_sel) *n_sel = b->tot_fin_sel;
+    return SMEM_OK;
+}
+
+// ---- final regions -> alignments, device-resident (smem_reg2aln's kernels over the batch's buffers)
+int smem_gpu_load_contigs(smem_gpu_t* g, int n_seqs, const int64_t* offset, const int32_t* len, int64_t l_pac) {
+    g_err[0] = 0;
+    if (!g || n_seqs <= 0 || !offset || !len || l_pac <= 0) return fail(SMEM_E_ARG, "smem_gpu_load_contigs: bad arguments");
+    int64_t at = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        if (offset[i] != at || len[i] <= 0)
+            return fail(SMEM_E_ARG, "smem_gpu_load_contigs: offsets must ascend from 0 with offset + len the next offset");
+        at += len[i];
+    }
+    if (at != l_pac) return fail(SMEM_E_ARG, "smem_gpu_load_contigs: the last contig does not end at l_pac");
+    gpu_wait(g);
+    // under the device lock and after every queued kernel, as smem_gpu_load_pac
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (int r = gpu_check(g)) return r;
+    HIP_TRY(hipSetDevice(g->device));
+    if (g->d_ctg_off) {
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(g->d_ctg_off);
+        (void)hipFree(g->d_ctg_len);
+        g->d_ctg_off = nullptr, g->d_ctg_len = nullptr;
+    }
+    g->n_ctg = 0, g->ctg_l_pac = 0;
+    int64_t* po = nullptr;
+    int32_t* pl = nullptr;
+    hipError_t e = hipMalloc(&po, sizeof(int64_t) * (size_t)n_seqs);
+    if (e == hipSuccess) e = hipMalloc(&pl, sizeof(int32_t) * (size_t)n_seqs);
+    if (e != hipSuccess) {
+        if (po) (void)hipFree(po);
+        return fail(SMEM_E_NOMEM, "smem_gpu_load_contigs: hipMalloc", e);
+    }
+    e = hipMemcpy(po, offset, sizeof(int64_t) * (size_t)n_seqs, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(pl, len, sizeof(int32_t) * (size_t)n_seqs, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(po);
+        (void)hipFree(pl);
+        return fail(SMEM_E_DEVICE, "smem_gpu_load_contigs: upload", e);
+    }
+    g->d_ctg_off = po, g->d_ctg_len = pl, g->n_ctg = n_seqs, g->ctg_l_pac = l_pac;
+    return SMEM_OK;
+}
+
+// device buffers of the stage for n_rec records (the pools are sized by the caller)
+static int g2a_bufs_size(G2aBufs& G, uint64_t n_rec) {
+    const uint64_t N = std::max<uint64_t>(n_rec, 1);
+    HIP_TRY(G.cnt.grow(smem::G2A_CNTS));
+    HIP_TRY(G.cur.grow(4));
+    HIP_TRY(G.task.grow(N));
+    HIP_TRY(G.list.grow(4 * N));
+    HIP_TRY(G.alns.grow(N));
+    HIP_TRY(G.rid.grow(N));
+    return SMEM_OK;
+}
+
+// CIGAR words and MD bytes a record: three times what 113,806 regions of 150 bp reads took
+// (5.5 words, 14.7 B: DESIGN.md §5); SMEM_G2A_POOL=<words>:<bytes> overrides, read at call time
+// (true: overridden -- the first pass then uses exactly that much, whatever the batch holds)
+static bool g2a_pool_estimate(uint64_t* words, uint64_t* bytes) {
+    *words = 16, *bytes = 48;
+    const char* e = getenv("SMEM_G2A_POOL");
+    if (!e || !*e) return false;
+    char* end = nullptr;
+    const unsigned long long w = strtoull(e, &end, 10);
+    if (end == e || *end != ':') return false;
+    const char* s = end + 1;
+    const unsigned long long m = strtoull(s, &end, 10);
+    if (end == s) return false;
+    *words = std::min<unsigned long long>(w, 1ull << 20), *bytes = std::min<unsigned long long>(m, 1ull << 20);
+    return true;
+}
+
+int smem_batch_reg2aln(smem_batch_t* b, const smem_aln_opt_t* opt, const uint64_t* idx, const uint64_t* idx_off) {
+    g_err[0] = 0;
+    if (!b || !b->fin_ran) return fail(SMEM_E_ARG, "smem_batch_reg2aln: run smem_batch_reg_finalize first");
+    if (!aln_opt_ok(opt)) return fail(SMEM_E_ARG, "smem_batch_reg2aln: scoring needs e >= 1, o >= 0, a >= 1, w >= 0");
+    smem_gpu_t* g = b->g;
+    if (!g->d_pac || g->l_pac <= 0) return fail(SMEM_E_ARG, "smem_batch_reg2aln: no resident .pac (smem_gpu_load_pac)");
+    if (idx && !idx_off) return fail(SMEM_E_ARG, "smem_batch_reg2aln: idx without idx_off");
+    const int n = b->n_reads;
+    uint64_t n_rec = b->tot_fin_sel;
+    if (idx_off) {  // the caller's selection: checked here against the totals, per read on the device
+        if (idx_off[0] != 0) return fail(SMEM_E_ARG, "smem_batch_reg2aln: idx_off must start at 0");
+        for (int r = 0; r < n; ++r)
+            if (idx_off[r + 1] < idx_off[r]) return fail(SMEM_E_ARG, "smem_batch_reg2aln: idx_off not ascending");
+        n_rec = idx_off[n];
+        if (n_rec > 0 && !idx) return fail(SMEM_E_ARG, "smem_batch_reg2aln: no idx");
+        for (uint64_t k = 0; k < n_rec; ++k)
+            if (idx[k] >= b->tot_fin) return fail(SMEM_E_ARG, "smem_batch_reg2aln: an index past the final regions");
+    }
+    if (n_rec >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_batch_reg2aln: too many records");
+    BatchCall call(b);
+    if (call.rc) return call.rc;
+    b->g2a_ran = b->g2a_fetched = false;
+    g->g2a_used.store(true);  // slots reserved from now on carry the stage's buffers
+    G2aBufs& G = b->g2a;
+    if (int rc = g2a_bufs_size(G, n_rec)) return rc;
+    HIP_TRY(b->h_g2a_ctr.grow(8));
+    uint64_t est_w = 0, est_m = 0;
+    const bool est_forced = g2a_pool_estimate(&est_w, &est_m);
+    HIP_TRY(G.cigar.grow(n_rec * est_w));
+    HIP_TRY(G.md.grow(n_rec * est_m));
+    b->g2a_own_idx = idx_off != nullptr;
+    if (idx_off) {
+        HIP_TRY(G.idx.grow(n_rec));
+        HIP_TRY(G.idx_off.grow((uint64_t)n + 1));
+        HIP_TRY(b->h_g2a_idx.grow(n_rec + (uint64_t)n + 1));  // pinned: the copies are asynchronous
+        if (n_rec) std::memcpy(b->h_g2a_idx.p, idx, sizeof(uint64_t) * n_rec);
+        std::memcpy(b->h_g2a_idx.p + n_rec, idx_off, sizeof(uint64_t) * ((size_t)n + 1));
+        if (n_rec) HIP_TRY(hipMemcpyAsync(G.idx.p, b->h_g2a_idx.p, sizeof(uint64_t) * n_rec, hipMemcpyHostToDevice, b->st));
+        HIP_TRY(hipMemcpyAsync(G.idx_off.p, b->h_g2a_idx.p + n_rec, sizeof(uint64_t) * ((size_t)n + 1),
+                               hipMemcpyHostToDevice, b->st));
+    }
+    b->tot_g2a = b->tot_g2a_cigar = b->tot_g2a_md = 0;
+    smem_batch_stats_t& S = b->stats;
+    S.g2a_ms = S.g2a_prep_ms = 0.0, S.n_g2a = S.n_g2a_deferred = S.n_g2a_xref = S.n_g2a_passes = 0;
+    if (n_rec == 0) {
+        INJECT(ST_G2A);
+        HIP_TRY(hipStreamSynchronize(b->st));
+        b->g2a_ran = true;
+        return SMEM_OK;
+    }
+    uint32_t* h_cnt = reinterpret_cast<uint32_t*>(b->h_g2a_ctr.p);
+    unsigned long long* h_cur = reinterpret_cast<unsigned long long*>(b->h_g2a_ctr.p + 4);
+    G2aPass R;
+    g2a_pass_params(R, opt, g->l_pac);
+    R.PP.regs = reinterpret_cast<const smem::G2aReg*>(b->fin.out_regs.p);
+    R.PP.idx = idx_off ? G.idx.p : b->fin.out_idx.p;
+    R.PP.rec_off = idx_off ? G.idx_off.p : b->fin.sel_off.p;
+    R.PP.reg_range = b->fin.out_off.p, R.PP.offs = b->d_offs.p;
+    R.PP.n_reads = (uint32_t)n, R.PP.n_rec = (uint32_t)n_rec;
+    if (g->d_ctg_off && g->ctg_l_pac == g->l_pac) R.PP.ctg = smem::G2aContigs{g->d_ctg_off, g->d_ctg_len, g->n_ctg};
+    R.PP.task = G.task.p, R.PP.list = G.list.p, R.PP.cnt = G.cnt.p, R.PP.cur = G.cur.p, R.PP.alns = G.alns.p;
+    R.PP.rid = G.rid.p;
+    R.P.codes = b->d_codes.p, R.P.pac = g->d_pac;
+    R.h_cnt = h_cnt, R.h_cur = h_cur, R.scratch = &G.scratch, R.ev = b->ev, R.inject = ST_G2A;
+    uint64_t cap_c = est_forced ? n_rec * est_w : G.cigar.n, cap_m = est_forced ? n_rec * est_m : G.md.n;
+    for (int pass = 0;; ++pass) {
+        R.P.cigar = G.cigar.p, R.P.md = G.md.p, R.P.cigar_cap = cap_c, R.P.md_cap = cap_m;
+        if (int rc = run_g2a(R, b->st)) return rc;
+        R.inject = -1;
+        S.g2a_ms += (double)R.ms_prep + (double)R.ms_dp, S.g2a_prep_ms += (double)R.ms_prep;
+        S.n_g2a_passes = (uint64_t)pass + 1;
+        if (h_cnt[smem::G2A_N_BADTRACE])
+            return fail(SMEM_E_INTERNAL, "smem_batch_reg2aln: a region's traceback left its band");
+        if (h_cur[0] <= cap_c && h_cur[1] <= cap_m) break;
+        if (pass) return fail(SMEM_E_INTERNAL, "smem_batch_reg2aln: the pools' second sizes did not hold");
+        // the cursors give the exact sizes; the kernels are deterministic, so one more pass fits
+        HIP_TRY(G.cigar.ensure(h_cur[0]));
+        HIP_TRY(G.md.ensure(h_cur[1]));
+        cap_c = G.cigar.n, cap_m = G.md.n;
+    }
+    b->tot_g2a = n_rec, b->tot_g2a_cigar = h_cur[0], b->tot_g2a_md = h_cur[1];
+    S.n_g2a = n_rec, S.n_g2a_deferred = h_cur[2], S.n_g2a_xref = h_cnt[smem::G2A_N_XREF];
+    b->g2a_ran = true;
+    return SMEM_OK;
+}
+
+int smem_batch_aln2_results(const smem_batch_t* b, const smem_aln_t** alns, const int32_t** rid,
+                            const uint64_t** aln_off, const uint32_t** cigar, uint64_t* n_cigar_words, const char** md,
+                            uint64_t* n_md_bytes, uint64_t* n_alns) {
+    if (!b || !b->g2a_fetched) return SMEM_E_ARG;
+    if (alns) *alns = reinterpret_cast<const smem_aln_t*>(b->h_g2a_alns.p);
+    if (rid) *rid = b->h_g2a_rid.p;
+    if (aln_off) *aln_off = b->h_g2a_off.p;
+    if (cigar) *cigar = b->h_g2a_cigar.p;
+    if (n_cigar_words) *n_cigar_words = b->tot_g2a_cigar;
+    if (md) *md = b->h_g2a_md.p;
+    if (n_md_bytes) *n_md_bytes = b->tot_g2a_md;
+    if (n_alns) *n_alns = b->tot_g2a;
     return SMEM_OK;
 }
 
@@ -3458,6 +3707,7 @@ static int collect_batch(smem_gpu_t* g, int slot, int n_reads, int max_len, uint
 // (no device work here or in smem_batch_create: smem_gpu_reserve_slots runs
 // both once with a measuring Arena, whose buffers are placeholders)
 static int fin_bufs_size(FinBufs& F, uint64_t n_reads, uint64_t n_regs);
+static int g2a_bufs_size(G2aBufs& G, uint64_t n_rec);
 static int batch_prealloc(smem_batch_t* b) {
     const uint64_t R = (uint64_t)b->max_reads;
     const uint64_t ni = R * 40, no = R * 16, nc = R * 6, ns = R * 12;
@@ -3491,6 +3741,12 @@ static int batch_prealloc(smem_batch_t* b) {
     HIP_TRY(b->d_aln_ctr.grow(smem::ALN_CTRS));
     if (b->g->fin_used.load())  // only where the stage is in use
         if (int rc = fin_bufs_size(b->fin, R, ns)) return rc;
+    if (b->g->g2a_used.load()) {  // ~1.2 records a read; the pools at the stage's own estimate
+        if (int rc = g2a_bufs_size(b->g2a, R * 2)) return rc;
+        HIP_TRY(b->g2a.cigar.grow(R * 2 * 16));
+        HIP_TRY(b->g2a.md.grow(R * 2 * 48));
+        HIP_TRY(b->h_g2a_ctr.grow(8));
+    }
     AlnHeavyBufs& H = b->aln_heavy;
     HIP_TRY(H.pre.grow(ns));
     HIP_TRY(H.pre_ok.grow(ns));

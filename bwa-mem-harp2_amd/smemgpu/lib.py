@@ -41,11 +41,13 @@ EXPORTED = [
     "smem_gpu_open_async", "smem_gpu_load_sa_async", "smem_gpu_load_pac_async",
     "smem_reg2aln",
     "smem_fin_opt_default", "smem_reg_finalize", "smem_batch_reg_finalize", "smem_batch_fin_results",
+    "smem_gpu_load_contigs", "smem_batch_reg2aln", "smem_batch_aln2_results",
 ]
 
 # smem_batch_fetch_mask bits (include/smem_gpu.h)
 FETCH_INTV, FETCH_SA, FETCH_CHAINS, FETCH_REGS, FETCH_ALL = 1, 2, 4, 8, 15
 FETCH_FIN = 16   # Batch.reg_finalize's results; not part of FETCH_ALL
+FETCH_ALN = 32   # Batch.reg2aln's results; not part of FETCH_ALL
 COLLECT_NO_FETCH = 1
 
 
@@ -107,7 +109,9 @@ class BatchStats(C.Structure):
                 ("sa_ms", C.c_double), ("n_occ", C.c_uint64), ("chain_ms", C.c_double), ("n_chains", C.c_uint64),
                 ("aln_ms", C.c_double), ("n_regs", C.c_uint64), ("t_start", C.c_uint64), ("t_end", C.c_uint64),
                 ("fin_ms", C.c_double), ("fin_lane_ms", C.c_double), ("fin_wave_ms", C.c_double),
-                ("n_fin", C.c_uint64), ("n_fin_sel", C.c_uint64)]
+                ("n_fin", C.c_uint64), ("n_fin_sel", C.c_uint64),
+                ("g2a_ms", C.c_double), ("g2a_prep_ms", C.c_double), ("n_g2a", C.c_uint64),
+                ("n_g2a_deferred", C.c_uint64), ("n_g2a_xref", C.c_uint64), ("n_g2a_passes", C.c_uint64)]
 
 
 class StreamStats(C.Structure):
@@ -185,7 +189,7 @@ ALNREG_DT = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4")
 ALN_DT = np.dtype([("pos", "<i8"), ("is_rev", "<i4"), ("n_cigar", "<i4"), ("NM", "<i4"), ("score", "<i4"),
                    ("tries", "<i4"), ("status", "<i4"), ("cigar_off", "<u8"), ("md_off", "<u8"), ("md_len", "<i4"),
                    ("pad", "<i4")])
-ALN_UNMAPPED, ALN_NOCIGAR, ALN_REJECT = 1, 2, 3
+ALN_UNMAPPED, ALN_NOCIGAR, ALN_REJECT, ALN_XREF = 1, 2, 3, 4
 FIN_SEL_DT = np.dtype([("mapq", "<i4"), ("flag", "<i4"), ("xs", "<i4")])   # smem_fin_sel_t
 SMEM_E_CAPACITY = -6
 
@@ -240,6 +244,11 @@ def load() -> C.CDLL:
     lib.smem_batch_fin_results.argtypes = [C.c_void_p, P(C.c_void_p), P(P(C.c_uint64)), P(C.c_void_p),
                                            P(P(C.c_uint64)), P(P(C.c_uint64)), P(P(C.c_int32)), P(C.c_uint64),
                                            P(C.c_uint64)]
+    lib.smem_gpu_load_contigs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.smem_batch_reg2aln.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.smem_batch_aln2_results.argtypes = [C.c_void_p, P(C.c_void_p), P(P(C.c_int32)), P(P(C.c_uint64)),
+                                            P(P(C.c_uint32)), P(C.c_uint64), P(C.c_void_p), P(C.c_uint64),
+                                            P(C.c_uint64)]
     lib.smem_chain_opt_default.argtypes = [P(ChainOptT)]
     lib.smem_chain_opt_default.restype = None
     lib.smem_batch_chain.argtypes = [C.c_void_p, C.c_int64, P(ChainOptT)]
@@ -473,6 +482,16 @@ class FinResults:
 
 
 @dataclass
+class AlnResults:
+    """final regions -> alignments (smem_batch_reg2aln)"""
+    alns: np.ndarray      # ALN_DT, one per record; status ALN_XREF: bwa_fix_xref2 is needed, the caller's
+    rid: np.ndarray       # int32, one per record: the contig of pos (-1: no alignment, or no contig table)
+    aln_off: np.ndarray   # (n_reads + 1,) uint64 into alns / rid: sel_off, or the caller's idx_off
+    cigar: np.ndarray     # uint32 words; record k's are cigar[cigar_off : cigar_off + n_cigar]
+    md: np.ndarray        # uint8; record k's MD is md[md_off : md_off + md_len]
+
+
+@dataclass
 class Results:
     intv: np.ndarray      # (N, 4) uint64: x0, x1, x2, info
     intv_off: np.ndarray  # (n_reads + 1,) uint64
@@ -486,6 +505,7 @@ class Results:
     regs: np.ndarray | None = None     # raw 64-byte smem_alnreg_t records, when Batch.chain2aln() ran
     reg_off: np.ndarray | None = None  # (n_reads + 1,) uint64
     fin: "FinResults | None" = None    # when Batch.reg_finalize() ran and FETCH_FIN was asked for
+    aln: "AlnResults | None" = None    # when Batch.reg2aln() ran and FETCH_ALN was asked for
 
     def read_chains(self, i: int) -> list:
         """read i's chains as [(pos, seeds)], in mem_chain(+flt) order."""
@@ -733,6 +753,16 @@ class Gpu:
             raise SmemError("load_pac: pac holds fewer than (l_pac + 3) / 4 bytes")
         _check(load().smem_gpu_load_pac(self._h, pac.ctypes.data, int(l_pac)), "smem_gpu_load_pac")
 
+    def load_contigs(self, offsets, lens, l_pac: int) -> None:
+        """Keep the contig table (bns->anns[].offset / .len) resident for
+        Batch.reg2aln (smem_gpu_load_contigs); it must tile [0, l_pac)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if offsets.size != lens.size:
+            raise SmemError("load_contigs: one length per offset")
+        _check(load().smem_gpu_load_contigs(self._h, offsets.size, offsets.ctypes.data, lens.ctypes.data, int(l_pac)),
+               "smem_gpu_load_contigs")
+
     def chain2aln(self, pac, l_pac: int, codes, offs, chains, chain_off, seeds, opt) -> tuple:
         """mem_chain2aln_short / mem_chain2aln of every chain of every read
         (software/bwamem.c:1452-1460) on this device.  opt is a ctypes struct
@@ -917,6 +947,23 @@ class Batch:
         _check(load().smem_batch_reg_finalize(self._h, ids.ctypes.data if ids is not None else None, int(id0),
                                               C.byref(opt)), "smem_batch_reg_finalize")
 
+    def reg2aln(self, opt, idx=None, idx_off=None) -> None:
+        """CIGAR, NM, MD, position and contig of every record of the last
+        reg_finalize(), over the final regions in HBM (smem_batch_reg2aln);
+        opt is laid out as smem_aln_opt_t.  idx / idx_off: the caller's own
+        records instead of the stage's selection, as indices into the final
+        regions with per-read offsets.  fetch(FETCH_ALN) returns them as .aln."""
+        if (idx is None) != (idx_off is None):
+            raise SmemError("reg2aln: idx and idx_off go together")
+        pi = po = None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.uint64)
+            idx_off = np.ascontiguousarray(idx_off, dtype=np.uint64)
+            if idx_off.size != self.n_reads + 1 or int(idx_off[-1]) != idx.size:
+                raise SmemError("reg2aln: idx_off must have n_reads + 1 entries and end at idx.size")
+            pi, po = idx.ctypes.data, idx_off.ctypes.data
+        _check(load().smem_batch_reg2aln(self._h, C.byref(opt), pi, po), "smem_batch_reg2aln")
+
     def debug_words(self, n_words: int) -> np.ndarray:
         out = np.zeros(n_words, dtype=np.uint64)
         rc = load().smem_batch_debug(self._h, out.ctypes.data, n_words)
@@ -978,6 +1025,18 @@ class Batch:
                 np.ctypeslib.as_array(fi, shape=(max(ks, 1),))[:ks].copy(),
                 np.ctypeslib.as_array(fso, shape=(n + 1,)).copy(),
                 np.ctypeslib.as_array(fst, shape=(max(n, 1),))[:n].copy(), self.stats()["fin_ms"])
+        al, cg, mdp = C.c_void_p(), C.POINTER(C.c_uint32)(), C.c_void_p()
+        ri, ao = C.POINTER(C.c_int32)(), C.POINTER(C.c_uint64)()
+        ncw, nmb, nal = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        if lib.smem_batch_aln2_results(self._h, C.byref(al), C.byref(ri), C.byref(ao), C.byref(cg), C.byref(ncw),
+                                       C.byref(mdp), C.byref(nmb), C.byref(nal)) == 0:
+            k, kc, km = int(nal.value), int(ncw.value), int(nmb.value)
+            res.aln = AlnResults(
+                np.frombuffer((C.c_char * (max(k, 1) * ALN_DT.itemsize)).from_address(al.value), dtype=ALN_DT)[:k].copy(),
+                np.ctypeslib.as_array(ri, shape=(max(k, 1),))[:k].copy(),
+                np.ctypeslib.as_array(ao, shape=(n + 1,)).copy(),
+                np.ctypeslib.as_array(cg, shape=(max(kc, 1),))[:kc].copy(),
+                np.frombuffer((C.c_char * max(km, 1)).from_address(mdp.value), dtype=np.uint8)[:km].copy())
         return res
 
     def close(self) -> None:

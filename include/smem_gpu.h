@@ -28,8 +28,8 @@
  * caller that takes its CPU path on SMEM_E_DEVICE computes exactly what the
  * reference computes.  Allocation failures are SMEM_E_NOMEM and leave the
  * device usable.  SMEM_GPU_FAIL=<stage>:<k>[:sticky] (stage: upload, seed,
- * sa, chain, aln, fin, fetch, any) injects SMEM_E_DEVICE into every k-th call of
- * the stage after its work is enqueued, to test that contract.
+ * sa, chain, aln, fin, g2a, fetch, any) injects SMEM_E_DEVICE into every k-th
+ * call of the stage after its work is enqueued, to test that contract.
  */
 #ifndef SMEM_GPU_H
 #define SMEM_GPU_H
@@ -308,6 +308,7 @@ int  smem_batch_fetch(smem_batch_t *b);
 #define SMEM_FETCH_REGS    8
 #define SMEM_FETCH_ALL    15
 #define SMEM_FETCH_FIN    16   /* smem_batch_reg_finalize's results (smem_batch_fin_results); not part of ALL */
+#define SMEM_FETCH_ALN    32   /* smem_batch_reg2aln's results (smem_batch_aln2_results); not part of ALL */
 int  smem_batch_fetch_mask(smem_batch_t *b, int mask);
 /* per-read view of fetched results: the concatenation of all smem_next2
  * lists in order (n_intv intervals) and the size of each list (n_calls) */
@@ -495,6 +496,9 @@ int  smem_batch_aln_results(const smem_batch_t *b, const smem_alnreg_t **regs, c
 #define SMEM_ALN_UNMAPPED 1
 #define SMEM_ALN_NOCIGAR  2
 #define SMEM_ALN_REJECT   3
+#define SMEM_ALN_XREF     4   /* smem_batch_reg2aln with a contig table only: the region bridges a contig
+                                 boundary (the test at the head of bwa_fix_xref2, software/bwa.c:195-199);
+                                 no alignment, the caller does it on the CPU */
 /* what mem_reg2aln (software/bwamem.c:1481-1553) makes of one region, short of
  * the contig lookup, MAPQ and flags */
 typedef struct {
@@ -519,7 +523,8 @@ typedef struct {
  * the resident .pac when pac == NULL.  regs[reg_off[r] .. reg_off[r+1]) are the
  * regions of read r in doubled coordinates, as smem_chain2aln returns them; rb,
  * re, qb, qe, truesc and w are read.  One smem_aln_t per region, in region
- * order; cigar_off / md_off need not ascend.  bwa_fix_xref2 (software/bwamem.c:1500)
+ * order; cigar_off / md_off need not ascend (the regions are classified and the
+ * output space is claimed on the device).  bwa_fix_xref2 (software/bwamem.c:1500)
  * needs the contig table and stays with the caller: every region must already
  * lie within one contig, and pos is in concatenated coordinates (contig id and
  * offset are the caller's).  Limits: qe - qb <= 1024 and re - rb <= 2048;
@@ -533,6 +538,34 @@ int  smem_reg2aln(smem_gpu_t *gpu, int n_reads, const uint8_t *codes, const uint
                   const uint8_t *pac, int64_t l_pac, const smem_aln_opt_t *opt,
                   smem_aln_t *alns, uint32_t *cigar, uint64_t cigar_cap, uint64_t *n_cigar_words,
                   char *md, uint64_t md_cap, uint64_t *n_md_bytes, double *kernel_ms);
+
+/* The contig table of the index, bns->anns[].offset / .len (software/bntseq.h), kept in HBM
+ * for smem_batch_reg2aln: uploaded once per handle (again: replaced), freed at shutdown.
+ * SMEM_E_ARG unless n_seqs > 0, offset[0] == 0, every len > 0, offset[i] + len[i] ==
+ * offset[i + 1] and the last contig ends at l_pac.  Optional: without it (or when its l_pac
+ * is not the resident .pac's) smem_batch_reg2aln gives rid -1 and marks nothing as bridging. */
+int  smem_gpu_load_contigs(smem_gpu_t *gpu, int n_seqs, const int64_t *offset, const int32_t *len, int64_t l_pac);
+/* Device-resident twin of smem_reg2aln: after smem_batch_reg_finalize, the alignment of every
+ * record of the batch over the final regions, the reads and the resident .pac still in HBM;
+ * no region, task or list crosses to the host.  idx == NULL: the records are
+ * regs_out[sel_idx[..]] of smem_batch_reg_finalize, per read by sel_off.  Else the caller's
+ * selection: idx[idx_off[r] .. idx_off[r + 1]) are read r's records as indices into the
+ * batch's final regions, each within the read's [out_off[r], out_off[r + 1]) (duplicates
+ * allowed); SMEM_E_ARG otherwise.  One smem_aln_t per record, as smem_reg2aln fills it, and
+ * one rid: with a contig table, bns_pos2rid of the final pos (software/bwamem.c:1548; pos
+ * itself stays in concatenated coordinates), and a region for which bwa_fix_xref2 would
+ * change something gets SMEM_ALN_XREF and no alignment; without one, -1.  The CIGAR / MD pools
+ * are the stage's own: sized from an estimate per record (SMEM_G2A_POOL=<words>:<bytes>
+ * overrides it) and, when too small, grown to the sizes the kernels report before one more
+ * pass -- the caller never sees SMEM_E_CAPACITY.  SMEM_E_ARG: smem_batch_reg_finalize has not
+ * run on this batch, no resident .pac, bad scoring.  smem_batch_fetch_mask(b, SMEM_FETCH_ALN)
+ * copies the results, smem_batch_aln2_results returns them (any pointer may be NULL; aln_off
+ * [n_reads + 1] is sel_off or idx_off).  A later smem_batch_chain2aln or
+ * smem_batch_reg_finalize on the batch ends them. */
+int  smem_batch_reg2aln(smem_batch_t *b, const smem_aln_opt_t *opt, const uint64_t *idx, const uint64_t *idx_off);
+int  smem_batch_aln2_results(const smem_batch_t *b, const smem_aln_t **alns, const int32_t **rid,
+                             const uint64_t **aln_off, const uint32_t **cigar, uint64_t *n_cigar_words,
+                             const char **md, uint64_t *n_md_bytes, uint64_t *n_alns);
 
 /* ------------------------------------------- raw regions -> final regions */
 /* the mem_opt_t fields the stage reads (software/bwamem.h:33-58) */
@@ -611,6 +644,11 @@ typedef struct {
 	double fin_ms;           /* smem_batch_reg_finalize kernels; fin_lane_ms / fin_wave_ms: its two tiers */
 	double fin_lane_ms, fin_wave_ms;
 	uint64_t n_fin, n_fin_sel; /* final regions, regions with a record */
+	double g2a_ms;           /* smem_batch_reg2aln: prep + DP kernels (every pass); g2a_prep_ms: the prep kernel */
+	double g2a_prep_ms;
+	uint64_t n_g2a;          /* records; n_g2a_deferred: regions redone by the scratch tier; n_g2a_xref: SMEM_ALN_XREF */
+	uint64_t n_g2a_deferred, n_g2a_xref;
+	uint64_t n_g2a_passes;   /* 1, or 2 when the CIGAR / MD pools had to grow */
 } smem_batch_stats_t;
 int  smem_batch_stats(const smem_batch_t *b, smem_batch_stats_t *st);
 
