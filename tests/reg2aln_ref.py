@@ -228,5 +228,82 @@ def reg2aln(opt, l_pac, pac, read, reg) -> Aln:                        # bwamem.
     return Aln(pos=pos, is_rev=int(is_rev), cigar=tuple(ops), NM=NM, score=score, tries=tries, status=0, md=md)
 
 
+# ---- where the GPU stage runs a region (csrc/global_kernels.h, g2a_prep_kernel) ----
+GROUPS = (16, 32, 64)                          # lanes of class 0 / 1 / 2; class 3 is the scratch tier
+LDS_BIG = 32768                                # G2A_LDS_BIG: the scratch-tier kernel's LDS
+SCRATCH_CLASS = 3
+
+
+def group_lds(group):                          # g2a_group_lds
+    return 8192 if group == 64 else 4096
+
+
+def first_w2(opt, ql, tl, truesc, reg_w):     # g2a_first_w2 (bwamem.c:1504-1508)
+    w2 = max(infer_bw(ql, tl, truesc, opt.a, opt.o_ins, opt.e_ins), infer_bw(ql, tl, truesc, opt.a, opt.o_del, opt.e_del))
+    return min(w2, reg_w) if w2 > opt.w else w2
+
+
+def band(opt, ql, tl, w_):                     # g2a_band (bwa.c:125-132)
+    max_gap = max(_c_div(((ql + 1) >> 1) * opt.a - opt.o_ins, opt.e_ins, 1.),
+                  _c_div(((ql + 1) >> 1) * opt.a - opt.o_del, opt.e_del, 1.), 1)
+    return max(min((max_gap + abs(tl - ql) + 1) >> 1, w_), abs(tl - ql) + 3)
+
+
+def row_bytes(ql, w):                          # g2a_row_bytes: 4 bits a cell
+    return (min(ql, 2 * w + 1) + 1) >> 1
+
+
+def fixed_bytes(ql, tl):                       # g2a_fixed_bytes: column array, query, target
+    return (ql + 1) * 8 + ((ql + 3) & ~3) + ((tl + 3) & ~3)
+
+
+def scratch_need(opt, ql, tl):                 # g2a_scratch_need: the band uncapped
+    return row_bytes(ql, band(opt, ql, tl, 0x7fffffff)) * tl
+
+
+@dataclass
+class Shape:
+    cls: int                                   # 0..2: 16 / 32 / 64 lanes, 3: scratch tier
+    n_col: list                                # per try; 0 where the try needs no DP (equal lengths, band 0)
+    nbytes: list                               # per try: fixed bytes + direction matrix
+    defer_try: int = 0                         # the 1-based try at which a lane-group kernel hands the region to
+                                               # the scratch tier (its matrix outgrew the group's LDS); 0: never
+
+    @property
+    def group(self):
+        return GROUPS[self.cls] if self.cls < SCRATCH_CLASS else 64
+
+    @property
+    def in_lds_tries(self):
+        """the tries the region's first kernel runs itself"""
+        return len(self.n_col) if not self.defer_try else self.defer_try - 1
+
+
+def classify(opt, reg, tries=3) -> Shape:
+    """The class g2a_prep_kernel gives an alignable region (from its first try's band), and
+    the column count and LDS bytes of each of its first `tries` tries (the band doubles;
+    how many tries there are is the scores' business: Aln.tries of reg2aln)."""
+    ql, tl = int(reg["qe"]) - int(reg["qb"]), int(reg["re"]) - int(reg["rb"])
+    w2 = first_w2(opt, ql, tl, int(reg["truesc"]), int(reg["w"]))
+    fixed = fixed_bytes(ql, tl)
+    n_col, nbytes = [], []
+    for _ in range(tries):
+        if ql == tl and w2 == 0:
+            n_col.append(0)
+            nbytes.append(fixed)
+        else:
+            w = band(opt, ql, tl, w2)
+            n_col.append(min(ql, 2 * w + 1))
+            nbytes.append(fixed + row_bytes(ql, w) * tl)
+        w2 <<= 1
+    cls = 0 if n_col[0] <= 16 else 1 if n_col[0] <= 32 else 2
+    while cls < SCRATCH_CLASS and nbytes[0] > group_lds(GROUPS[cls]):
+        cls += 1
+    defer = 0
+    if cls < SCRATCH_CLASS:
+        defer = next((t + 1 for t in range(tries) if nbytes[t] > group_lds(GROUPS[cls])), 0)
+    return Shape(cls, n_col, nbytes, defer)
+
+
 def cigar_str(ops) -> str:
     return "".join(f"{int(c) >> 4}{'MIDS'[int(c) & 0xf]}" for c in ops)

@@ -352,17 +352,8 @@ def _synthetic_ref(name):
 
 
 def _n_col(o, reg):
-    ql, tl = int(reg["qe"] - reg["qb"]), int(reg["re"] - reg["rb"])
-    w2 = max(ref.infer_bw(ql, tl, int(reg["truesc"]), o.a, o.o_del, o.e_del),
-             ref.infer_bw(ql, tl, int(reg["truesc"]), o.a, o.o_ins, o.e_ins))
-    if w2 > o.w:
-        w2 = min(w2, int(reg["w"]))
-    if ql == tl and w2 == 0:
-        return 0
-    mg = max(ref._c_div(((ql + 1) >> 1) * o.a - o.o_ins, o.e_ins, 1.), ref._c_div(((ql + 1) >> 1) * o.a - o.o_del,
-                                                                                  o.e_del, 1.), 1)
-    w = max(min((mg + abs(tl - ql) + 1) >> 1, w2), abs(tl - ql) + 3)
-    return min(ql, 2 * w + 1)
+    """columns of the region's first try (0: no DP), by the restated classifier"""
+    return ref.classify(o, reg, 1).n_col[0]
 
 
 def test_synthetic_regions_hit_their_shapes():

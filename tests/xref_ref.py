@@ -65,31 +65,26 @@ def reads_of(name):
     return golden_data.aln_reads(next(f for f in golden_data.aln_fixtures() if f["file"] == name + ".smrg.gz"))
 
 
-@functools.lru_cache(maxsize=None)
-def _aligned(name):
-    """reg2aln_ref.reg2aln over every selected final region of a set (computed once):
-    per read a list of (final region, Aln) in selection order"""
+def aligned_rows(fin_rows, l_pac, pac, reads, opt=None, align=None):
+    """reg2aln_ref.reg2aln under scoring `opt` over every selected final region of
+    finalize()'s per-read output (a, sel, idx): per read a list of (final region, Aln) in
+    selection order.  align(r, region) replaces the plain call (a caller's cache)."""
     import reg2aln_ref
-    import regfin_data as D
-    from tests import golden_data
-    F = D.load(name)
-    pac, reads = golden_data.pac(F["g"]), reads_of(name)
-    return [[(a[k], reg2aln_ref.reg2aln(reg2aln_ref.Opt(), F["l_pac"], pac, reads.read(r), a[k])) for k in idx]
-            for r, (a, _sel, idx) in enumerate(D.restated(name)[0])]
+    opt = opt or reg2aln_ref.Opt()
+    if align is None:
+        def align(r, p):
+            return reg2aln_ref.reg2aln(opt, l_pac, pac, reads.read(r), p)
+    return [[(a[k], align(r, a[k])) for k in idx] for r, (a, _sel, idx) in enumerate(fin_rows)]
 
 
-def expected(name, with_contigs=True):
-    """what smem_batch_reg2aln gives for the selection of regfin_data set `name`: per read a
-    list of (final region, reg2aln_ref.Aln, rid) in selection order; a region that needs
-    bwa_fix_xref2 carries Aln(status=XREF) and rid -1.  Without contigs nothing is marked
-    and every rid is -1."""
+def expected_rows(rows, contigs, l_pac, with_contigs=True):
+    """aligned_rows' output with the contig lookup applied: per read a list of (final
+    region, reg2aln_ref.Aln, rid); a region that needs bwa_fix_xref2 carries
+    Aln(status=XREF) and rid -1.  Without contigs nothing is marked and every rid is -1."""
     import reg2aln_ref
-    import regfin_data as D
-    F = D.load(name)
-    _names, offs, lens = table(F["contigs"])
-    l_pac = F["l_pac"]
+    _names, offs, lens = table(contigs)
     out = []
-    for row in _aligned(name):
+    for row in rows:
         got = []
         for p, aln in row:
             rid = -1
@@ -101,3 +96,20 @@ def expected(name, with_contigs=True):
             got.append((p, aln, rid))
         out.append(got)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def _aligned(name):
+    """aligned_rows over a regfin_data set at the default options (computed once)"""
+    import regfin_data as D
+    from tests import golden_data
+    F = D.load(name)
+    return aligned_rows(D.restated(name)[0], F["l_pac"], golden_data.pac(F["g"]), reads_of(name))
+
+
+def expected(name, with_contigs=True):
+    """what smem_batch_reg2aln gives for the selection of regfin_data set `name` at the
+    default options (expected_rows)"""
+    import regfin_data as D
+    F = D.load(name)
+    return expected_rows(_aligned(name), F["contigs"], F["l_pac"], with_contigs)
