@@ -39,6 +39,7 @@
 #include "aln_kernels.h"
 #include "global_kernels.h"
 #include "fin_kernels.h"
+#include "sam_kernels.h"
 
 using smem::Intv;
 
@@ -96,13 +97,13 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
 // the drain on the way out is what keeps that work from landing after the
 // caller resumed.  stage: upload (smem_batch_set_reads*), seed
 // (smem_batch_run), sa, chain, aln (smem_batch_chain2aln), fin (smem_reg_finalize,
-// smem_batch_reg_finalize), g2a (smem_batch_reg2aln), fetch, or any.
+// smem_batch_reg_finalize), g2a (smem_batch_reg2aln), sam (smem_batch_sam, smem_sam_text), fetch, or any.
 // ":sticky" also marks the device faulted, as a real runtime failure does;
 // ":hip=<code>" goes through fail() with that hipError_t, so the
 // classification decides (hip=9, hipErrorInvalidConfiguration: that call only;
 // hip=719, hipErrorLaunchFailure: the device).
-enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_G2A, ST_N };
-const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin", "g2a"};
+enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_G2A, ST_SAM, ST_N };
+const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin", "g2a", "sam"};
 std::atomic<uint64_t> g_stage_calls[ST_N];
 
 int inject_fault(int stage) {
@@ -330,6 +331,11 @@ struct smem_gpu {
     int n_ctg = 0;
     int64_t ctg_l_pac = 0;
     std::atomic<bool> g2a_used{false};  // as fin_used, for smem_batch_reg2aln's buffers
+    // bns->anns[].name beside the contig table (smem_gpu_load_contig_names): n_ctg names, their offsets
+    char* d_ctg_names = nullptr;
+    uint64_t* d_ctg_name_off = nullptr;
+    int n_ctg_names = 0;
+    std::atomic<bool> sam_used{false};  // as fin_used, for smem_batch_sam's buffers
     int64_t l_pac = 0;
     uint64_t n_sa = 0;
     uint32_t sa_shift = 0;
@@ -471,6 +477,24 @@ struct G2aBufs {
     }
 };
 
+// device buffers of alignments -> SAM text (csrc/sam_kernels.h SamParams); names .. rg: the
+// read text of smem_batch_set_read_text and the call's read-group id
+struct SamBufs {
+    DevBuf<char> names, qual, comments, rg, text;
+    DevBuf<uint64_t> name_off, comment_off, read_bytes, text_off;
+    DevBuf<uint32_t> rec_len, sa_len, cnt;
+    DevBuf<int32_t> status;
+    DevBuf<uint8_t> scan_tmp;
+    template <class F>
+    void each(F&& f) {
+        f(names); f(qual); f(comments); f(rg); f(text); f(name_off); f(comment_off); f(read_bytes); f(text_off);
+        f(rec_len); f(sa_len); f(cnt); f(status); f(scan_tmp);
+    }
+    void release() {
+        each([](auto& x) { x.release(); });
+    }
+};
+
 struct smem_batch {
     smem_gpu_t* g = nullptr;
     char* arena_dev = nullptr;   // the blocks a reserved slot's buffers are carved from (Arena)
@@ -572,6 +596,18 @@ struct smem_batch {
     HostBuf<char> h_g2a_md;
     bool g2a_ran = false, g2a_fetched = false, g2a_own_idx = false;
     uint64_t tot_g2a = 0, tot_g2a_cigar = 0, tot_g2a_md = 0;
+    bool g2a_with_ctg = false;                // the last smem_batch_reg2aln looked its records up in the contig table
+    // SAM text (smem_batch_set_read_text, smem_batch_sam): nothing here is allocated until they are called
+    SamBufs sam;
+    HostBuf<uint8_t> h_sam_stage;             // the read text on its way up: both offset arrays, names, qual, comments
+    HostBuf<uint64_t> h_sam_ctr;              // [0] the text's size, [1] the u32 counters; [2, ..) the read-group id
+    HostBuf<char> h_sam_text;
+    HostBuf<uint64_t> h_sam_off;              // text_off[n + 1]
+    HostBuf<int32_t> h_sam_status;
+    bool text_set = false, text_qual = false, text_comments = false;
+    bool sam_ran = false, sam_fetched = false;
+    uint64_t tot_sam = 0;
+    smem_sam_stats_t sam_stats{};
     smem_batch_stats_t stats{};
 };
 
@@ -595,6 +631,7 @@ static void batch_bufs(smem_batch_t* b, D&& d, H&& h) {
     h(b->h_fin_status);
     b->g2a.each(d); h(b->h_g2a_idx); h(b->h_g2a_ctr); h(b->h_g2a_off); h(b->h_g2a_alns); h(b->h_g2a_rid);
     h(b->h_g2a_cigar); h(b->h_g2a_md);
+    b->sam.each(d); h(b->h_sam_stage); h(b->h_sam_ctr); h(b->h_sam_text); h(b->h_sam_off); h(b->h_sam_status);
     h(b->h_ctr); h(b->h_tot); h(b->h_intv); h(b->h_calls);
     d(b->d_pintv); h(b->h_pintv); h(b->h_intv_off); h(b->h_call_off);
 }
@@ -855,6 +892,7 @@ static int gpu_open(smem_gpu_t* g, const uint32_t* bwt) {
     if (e == hipSuccess) e = smem_preload_chain();
     if (e == hipSuccess) e = smem_preload_ksw();
     if (e == hipSuccess) e = smem_preload_aln();
+    if (e == hipSuccess) e = smem_preload_sam();
     if (e != hipSuccess) return fail(SMEM_E_DEVICE, "smem_gpu_init: code objects", e);
     // the default kernel's k-mer table (the index is constant for the handle's life), built where the
     // Occ64 layout above is: on the null stream, before any batch exists.  A table that cannot be
@@ -1132,6 +1170,8 @@ void smem_gpu_shutdown(smem_gpu_t* g) {
     if (g->d_fin_subn) (void)hipFree(g->d_fin_subn);
     if (g->d_ctg_off) (void)hipFree(g->d_ctg_off);
     if (g->d_ctg_len) (void)hipFree(g->d_ctg_len);
+    if (g->d_ctg_names) (void)hipFree(g->d_ctg_names);
+    if (g->d_ctg_name_off) (void)hipFree(g->d_ctg_name_off);
     for (auto& p : g->pairs) {
         (void)hipStreamDestroy(p.first);
         (void)hipStreamDestroy(p.second);
@@ -1217,6 +1257,7 @@ static int upload_reads(smem_batch_t* b, int n_reads) {
     for (int i = 0; i < n_reads; ++i) ml = std::max<int>(ml, (int)(b->h_offs.p[i + 1] - b->h_offs.p[i]));
     b->read_len_max = ml;
     b->ran = b->fetched = false;
+    b->text_set = b->sam_ran = b->sam_fetched = false;  // the read text belongs to the reads it came with
     b->n_reads = 0;
     const uint64_t nb = b->h_offs.p[n_reads];
     HIP_TRY(hipMemcpyAsync(b->d_codes.p, b->h_codes.p, std::max<uint64_t>(nb, 1), hipMemcpyHostToDevice, b->st));
@@ -1304,7 +1345,7 @@ static int batch_run_impl(smem_batch_t* b, const smem_opt_t* opt) {
     b->chain_ran = b->chain_fetched = false;
     b->tot_chains = b->tot_seeds = 0;
     b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     b->tot_regs = 0;
     b->stats = smem_batch_stats_t{};
     b->stats.block = 256;
@@ -1443,11 +1484,13 @@ static int fetch_impl(smem_batch_t* b, int mask) {
     if (call.rc) return call.rc;
     // views of an earlier fetch end here (its buffers may be regrown below)
     b->fetched = b->sa_fetched = b->chain_fetched = b->aln_fetched = b->fin_fetched = b->g2a_fetched = false;
+    b->sam_fetched = false;
     const int n = b->n_reads;
     const bool f_intv = mask & SMEM_FETCH_INTV, f_sa = (mask & SMEM_FETCH_SA) && b->sa_ran;
     const bool f_chain = (mask & SMEM_FETCH_CHAINS) && b->chain_ran, f_aln = (mask & SMEM_FETCH_REGS) && b->aln_ran;
     const bool f_fin = (mask & SMEM_FETCH_FIN) && b->fin_ran;
     const bool f_g2a = (mask & SMEM_FETCH_ALN) && b->g2a_ran;
+    const bool f_sam = (mask & SMEM_FETCH_SAM) && b->sam_ran;
     // pinned result buffers grow with headroom: a streamed batch whose next
     // chunk holds a few more intervals must not re-pin a gigabyte
     if (!f_intv) {
@@ -1552,8 +1595,22 @@ static int fetch_impl(smem_batch_t* b, int mask) {
         if (b->tot_g2a_md)
             HIP_TRY(hipMemcpyAsync(b->h_g2a_md.p, b->g2a.md.p, b->tot_g2a_md, hipMemcpyDeviceToHost, b->st));
     }
+    if (f_sam) {
+        HIP_TRY(b->h_sam_off.grow((uint64_t)n + 1));
+        HIP_TRY(b->h_sam_status.grow((uint64_t)std::max(n, 1)));
+        HIP_TRY(b->h_sam_text.grow(b->tot_sam));
+        if (n > 0) {
+            HIP_TRY(hipMemcpyAsync(b->h_sam_off.p, b->sam.text_off.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, b->st));
+            HIP_TRY(hipMemcpyAsync(b->h_sam_status.p, b->sam.status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, b->st));
+        } else {
+            b->h_sam_off.p[0] = 0;
+        }
+        if (b->tot_sam)
+            HIP_TRY(hipMemcpyAsync(b->h_sam_text.p, b->sam.text.p, b->tot_sam, hipMemcpyDeviceToHost, b->st));
+    }
     INJECT(ST_FETCH);
     HIP_TRY(hipStreamSynchronize(b->st));
+    b->sam_fetched = f_sam;
     b->fin_fetched = f_fin;
     b->g2a_fetched = f_g2a;
     b->fetched = f_intv;
@@ -1572,10 +1629,10 @@ int smem_batch_fetch(smem_batch_t* b) {
 int smem_batch_fetch_mask(smem_batch_t* b, int mask) {
     g_err[0] = 0;
     if (!b || !b->ran) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: batch has not run");
-    if (mask & ~(SMEM_FETCH_ALL | SMEM_FETCH_FIN | SMEM_FETCH_ALN)) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: unknown bits");
+    if (mask & ~(SMEM_FETCH_ALL | SMEM_FETCH_FIN | SMEM_FETCH_ALN | SMEM_FETCH_SAM)) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: unknown bits");
     if (((mask & SMEM_FETCH_SA) && !b->sa_ran) || ((mask & SMEM_FETCH_CHAINS) && !b->chain_ran) ||
         ((mask & SMEM_FETCH_REGS) && !b->aln_ran) || ((mask & SMEM_FETCH_FIN) && !b->fin_ran) ||
-        ((mask & SMEM_FETCH_ALN) && !b->g2a_ran))
+        ((mask & SMEM_FETCH_ALN) && !b->g2a_ran) || ((mask & SMEM_FETCH_SAM) && !b->sam_ran))
         return fail(SMEM_E_ARG, "smem_batch_fetch_mask: a requested stage has not run on this batch");
     return fetch_impl(b, mask);
 }
@@ -1749,7 +1806,7 @@ int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
     if (call.rc) return call.rc;
     b->sa_ran = b->chain_ran = b->aln_ran = false;
     b->sa_fetched = b->chain_fetched = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     // the densified SA may still be in the making (smem_gpu_load_sa runs it
     // in the background): until its event has passed, the walk goes to the
     // stored samples instead (the same positions, sa_intv / D times the LF
@@ -1816,7 +1873,7 @@ int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
     b->sa_min_seed_len = min_seed_len;
     b->chain_ran = b->chain_fetched = false;
     b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     return SMEM_OK;
 }
 
@@ -1838,7 +1895,7 @@ int smem_batch_chain(smem_batch_t* b, int64_t l_pac, const smem_chain_opt_t* opt
     if (call.rc) return call.rc;
     b->chain_ran = b->aln_ran = false;
     b->chain_fetched = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     const int n = b->n_reads;
     const uint64_t no = std::max<uint64_t>(b->tot_occ, 1);
     HIP_TRY(b->d_seed.grow(no));
@@ -1946,7 +2003,7 @@ int smem_batch_chain(smem_batch_t* b, int64_t l_pac, const smem_chain_opt_t* opt
     b->chain_fetched = false;
     b->chain_filtered = opt->filter != 0;
     b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     return SMEM_OK;
 }
 
@@ -2644,7 +2701,7 @@ int smem_batch_chain2aln(smem_batch_t* b, const smem_aln_opt_t* opt) {
     BatchCall call(b, aln_two_streams());
     if (call.rc) return call.rc;
     b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     const int n = b->n_reads;
     const uint64_t ns = std::max<uint64_t>(b->tot_seeds, 1);
     HIP_TRY(b->d_aln_srt.grow(ns + 1));
@@ -3270,7 +3327,7 @@ int smem_batch_reg_finalize(smem_batch_t* b, const int64_t* ids, int64_t id0, co
     smem_gpu_t* g = b->g;
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = false;
+    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     g->fin_used.store(true);  // slots reserved from now on carry the stage's buffers
     const int n = b->n_reads;
     if (int rc = fin_tables(g)) return rc;
@@ -3346,6 +3403,12 @@ int smem_gpu_load_contigs(smem_gpu_t* g, int n_seqs, const int64_t* offset, cons
         g->d_ctg_off = nullptr, g->d_ctg_len = nullptr;
     }
     g->n_ctg = 0, g->ctg_l_pac = 0;
+    if (g->d_ctg_names) {  // the names belonged to the table this call replaces
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(g->d_ctg_names);
+        (void)hipFree(g->d_ctg_name_off);
+        g->d_ctg_names = nullptr, g->d_ctg_name_off = nullptr, g->n_ctg_names = 0;
+    }
     int64_t* po = nullptr;
     int32_t* pl = nullptr;
     hipError_t e = hipMalloc(&po, sizeof(int64_t) * (size_t)n_seqs);
@@ -3415,7 +3478,7 @@ int smem_batch_reg2aln(smem_batch_t* b, const smem_aln_opt_t* opt, const uint64_
     if (n_rec >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_batch_reg2aln: too many records");
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->g2a_ran = b->g2a_fetched = false;
+    b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     g->g2a_used.store(true);  // slots reserved from now on carry the stage's buffers
     G2aBufs& G = b->g2a;
     if (int rc = g2a_bufs_size(G, n_rec)) return rc;
@@ -3454,6 +3517,7 @@ int smem_batch_reg2aln(smem_batch_t* b, const smem_aln_opt_t* opt, const uint64_
     R.PP.reg_range = b->fin.out_off.p, R.PP.offs = b->d_offs.p;
     R.PP.n_reads = (uint32_t)n, R.PP.n_rec = (uint32_t)n_rec;
     if (g->d_ctg_off && g->ctg_l_pac == g->l_pac) R.PP.ctg = smem::G2aContigs{g->d_ctg_off, g->d_ctg_len, g->n_ctg};
+    b->g2a_with_ctg = R.PP.ctg.off != nullptr;
     R.PP.task = G.task.p, R.PP.list = G.list.p, R.PP.cnt = G.cnt.p, R.PP.cur = G.cur.p, R.PP.alns = G.alns.p;
     R.PP.rid = G.rid.p;
     R.P.codes = b->d_codes.p, R.P.pac = g->d_pac;
@@ -3492,6 +3556,398 @@ int smem_batch_aln2_results(const smem_batch_t* b, const smem_aln_t** alns, cons
     if (md) *md = b->h_g2a_md.p;
     if (n_md_bytes) *n_md_bytes = b->tot_g2a_md;
     if (n_alns) *n_alns = b->tot_g2a;
+    return SMEM_OK;
+}
+
+// ---- alignments -> SAM text (mem_reg2sam_se / mem_aln2sam, software/bwamem.c:1214-1393: csrc/sam_kernels.hip)
+static_assert(sizeof(smem_sam_rec_t) == sizeof(smem::SamRec), "record layout");
+static_assert(SMEM_SAM_HOST == smem::SAM_HOST, "status values");
+constexpr size_t SAM_RG_MAX = 1023;
+
+int smem_gpu_load_contig_names(smem_gpu_t* g, int n_seqs, const char* names, const uint64_t* name_off) {
+    g_err[0] = 0;
+    if (!g || n_seqs <= 0 || !names || !name_off) return fail(SMEM_E_ARG, "smem_gpu_load_contig_names: bad arguments");
+    for (int i = 0; i < n_seqs; ++i)
+        if (name_off[i + 1] < name_off[i]) return fail(SMEM_E_ARG, "smem_gpu_load_contig_names: name_off not ascending");
+    gpu_wait(g);
+    // under the device lock and after every queued kernel, as smem_gpu_load_contigs
+    std::lock_guard<std::mutex> lk(g->mu);
+    if (int r = gpu_check(g)) return r;
+    if (!g->d_ctg_off || g->n_ctg != n_seqs)
+        return fail(SMEM_E_ARG, "smem_gpu_load_contig_names: no contig table of n_seqs contigs (smem_gpu_load_contigs)");
+    HIP_TRY(hipSetDevice(g->device));
+    if (g->d_ctg_names) {
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(g->d_ctg_names);
+        (void)hipFree(g->d_ctg_name_off);
+        g->d_ctg_names = nullptr, g->d_ctg_name_off = nullptr, g->n_ctg_names = 0;
+    }
+    const uint64_t o0 = name_off[0], nb = name_off[n_seqs] - o0;
+    std::vector<uint64_t> off((size_t)n_seqs + 1);
+    for (int i = 0; i <= n_seqs; ++i) off[(size_t)i] = name_off[i] - o0;
+    char* pn = nullptr;
+    uint64_t* po = nullptr;
+    hipError_t e = hipMalloc(&pn, std::max<uint64_t>(nb, 1));
+    if (e == hipSuccess) e = hipMalloc(&po, sizeof(uint64_t) * off.size());
+    if (e != hipSuccess) {
+        if (pn) (void)hipFree(pn);
+        return fail(SMEM_E_NOMEM, "smem_gpu_load_contig_names: hipMalloc", e);
+    }
+    if (nb) e = hipMemcpy(pn, names + o0, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(po, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(pn);
+        (void)hipFree(po);
+        return fail(SMEM_E_DEVICE, "smem_gpu_load_contig_names: upload", e);
+    }
+    g->d_ctg_names = pn, g->d_ctg_name_off = po, g->n_ctg_names = n_seqs;
+    return SMEM_OK;
+}
+
+int smem_batch_set_read_text(smem_batch_t* b, const char* names, const uint64_t* name_off, const char* qual,
+                             const char* comments, const uint64_t* comment_off) {
+    g_err[0] = 0;
+    if (!b || !names || !name_off || (comments && !comment_off))
+        return fail(SMEM_E_ARG, "smem_batch_set_read_text: bad arguments");
+    const int n = b->n_reads;
+    for (int r = 0; r < n; ++r) {
+        if (name_off[r + 1] < name_off[r]) return fail(SMEM_E_ARG, "smem_batch_set_read_text: name_off not ascending");
+        if (name_off[r + 1] - name_off[r] > (uint64_t)smem::SAM_NAME_MAX)
+            return fail(SMEM_E_ARG, "smem_batch_set_read_text: a name of more than 255 bytes");
+        if (comments && comment_off[r + 1] < comment_off[r])
+            return fail(SMEM_E_ARG, "smem_batch_set_read_text: comment_off not ascending");
+    }
+    const uint64_t N = (uint64_t)n + 1, nn = name_off[n] - name_off[0], nq = qual ? b->h_offs.p[n] : 0;
+    const uint64_t nc = comments ? comment_off[n] - comment_off[0] : 0;
+    BatchCall call(b);
+    if (call.rc) return call.rc;
+    b->text_set = b->sam_ran = b->sam_fetched = false;
+    SamBufs& S = b->sam;
+    HIP_TRY(S.name_off.grow(N));
+    HIP_TRY(S.names.grow(nn));
+    if (qual) HIP_TRY(S.qual.grow(nq));
+    if (comments) {
+        HIP_TRY(S.comment_off.grow(N));
+        HIP_TRY(S.comments.grow(nc));
+    }
+    // pinned staging (the copies are asynchronous): both offset arrays from 0, then the bytes
+    HIP_TRY(b->h_sam_stage.grow(16 * N + nn + nq + nc));
+    uint64_t* ho = reinterpret_cast<uint64_t*>(b->h_sam_stage.p);
+    char* hb = reinterpret_cast<char*>(b->h_sam_stage.p) + 16 * N;
+    for (uint64_t r = 0; r < N; ++r) {
+        ho[r] = name_off[r] - name_off[0];
+        ho[N + r] = comments ? comment_off[r] - comment_off[0] : 0;
+    }
+    if (nn) std::memcpy(hb, names + name_off[0], nn);
+    if (nq) std::memcpy(hb + nn, qual, nq);
+    if (nc) std::memcpy(hb + nn + nq, comments + comment_off[0], nc);
+    HIP_TRY(hipMemcpyAsync(S.name_off.p, ho, 8 * N, hipMemcpyHostToDevice, b->st));
+    if (nn) HIP_TRY(hipMemcpyAsync(S.names.p, hb, nn, hipMemcpyHostToDevice, b->st));
+    if (nq) HIP_TRY(hipMemcpyAsync(S.qual.p, hb + nn, nq, hipMemcpyHostToDevice, b->st));
+    if (comments) HIP_TRY(hipMemcpyAsync(S.comment_off.p, ho + N, 8 * N, hipMemcpyHostToDevice, b->st));
+    if (nc) HIP_TRY(hipMemcpyAsync(S.comments.p, hb + nn + nq, nc, hipMemcpyHostToDevice, b->st));
+    INJECT(ST_UPLOAD);
+    HIP_TRY(hipStreamSynchronize(b->st));
+    b->text_set = true, b->text_qual = qual != nullptr, b->text_comments = comments != nullptr;
+    return SMEM_OK;
+}
+
+// device buffers of the stage for n_reads reads of n_rec records (the text is sized by the caller)
+static int sam_bufs_size(SamBufs& S, uint64_t n_reads, uint64_t n_rec) {
+    const uint64_t R = std::max<uint64_t>(n_reads, 1), N = std::max<uint64_t>(n_rec, 1);
+    HIP_TRY(S.cnt.grow(smem::SAM_CNTS));
+    HIP_TRY(S.rec_len.grow(N));
+    HIP_TRY(S.sa_len.grow(N));
+    HIP_TRY(S.read_bytes.grow(R));
+    HIP_TRY(S.text_off.grow(R + 1));
+    HIP_TRY(S.status.grow(R));
+    HIP_TRY(S.rg.grow(SAM_RG_MAX + 1));
+    size_t tmp = 0;
+    HIP_TRY(smem_launch_offsets(nullptr, nullptr, (int)R, nullptr, &tmp, nullptr));
+    HIP_TRY(S.scan_tmp.grow(tmp + 256));
+    return SMEM_OK;
+}
+
+// the text a batch's first call allocates: a line is the read twice (SEQ, QUAL) and ~100 bytes
+// of fields and tags; a batch that needs more grows to its total
+static uint64_t sam_text_estimate(uint64_t n_reads, uint64_t n_rec, uint64_t n_bases) {
+    return 2 * n_bases + n_bases / 2 + 160 * (n_rec + n_reads) + 256;
+}
+
+// One call's two passes, shared by smem_batch_sam and smem_sam_text: the caller fills P's inputs
+// and the length pass's buffers; run_sam_len enqueues the length kernels and the scan and waits
+// for the 8-byte total, run_sam_write (P.text set by then) the write kernel and its counters.
+struct SamPass {
+    smem::SamParams P;
+    uint64_t* read_bytes = nullptr;  // the scan's input (P.read_bytes) and output (P.text_off), non-const
+    uint64_t* text_off = nullptr;
+    DevBuf<uint8_t>* scan_tmp = nullptr;
+    uint64_t* h_ctr = nullptr;       // host (pinned in a batch): [0] the total, [1] the u32 counters
+    hipEvent_t* ev = nullptr;        // 4 events
+    int inject = -1;
+    float ms_len = 0.f, ms_write = 0.f;
+};
+
+static int run_sam_len(SamPass& R, hipStream_t st) {
+    const int n = (int)R.P.n_reads;
+    HIP_TRY(hipMemsetAsync(R.P.cnt, 0, sizeof(uint32_t) * smem::SAM_CNTS, st));
+    HIP_TRY(hipEventRecord(R.ev[0], st));
+    HIP_TRY(smem_launch_sam_len(&R.P, st));
+    size_t tmp = R.scan_tmp->n;
+    HIP_TRY(smem_launch_offsets(R.read_bytes, R.text_off, n, R.scan_tmp->p, &tmp, st));
+    HIP_TRY(hipEventRecord(R.ev[1], st));
+    HIP_TRY(hipMemcpyAsync(R.h_ctr, R.text_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (R.inject >= 0) INJECT(R.inject);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&R.ms_len, R.ev[0], R.ev[1]));
+    return SMEM_OK;
+}
+
+static int run_sam_write(SamPass& R, hipStream_t st) {
+    HIP_TRY(hipEventRecord(R.ev[2], st));
+    HIP_TRY(smem_launch_sam_write(&R.P, st));
+    HIP_TRY(hipEventRecord(R.ev[3], st));
+    HIP_TRY(hipMemcpyAsync(R.h_ctr + 1, R.P.cnt, sizeof(uint32_t) * smem::SAM_CNTS, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&R.ms_write, R.ev[2], R.ev[3]));
+    const uint32_t* cnt = reinterpret_cast<const uint32_t*>(R.h_ctr + 1);
+    if (cnt[smem::SAM_N_BADLEN]) return fail(SMEM_E_INTERNAL, "SAM text: a read's lines differ in size from its counted bytes");
+    return SMEM_OK;
+}
+
+int smem_batch_sam(smem_batch_t* b, const smem_sam_opt_t* opt) {
+    g_err[0] = 0;
+    if (!b || !b->g2a_ran) return fail(SMEM_E_ARG, "smem_batch_sam: run smem_batch_reg2aln first");
+    if (b->g2a_own_idx)
+        return fail(SMEM_E_ARG, "smem_batch_sam: smem_batch_reg2aln ran over the caller's index lists (no MAPQ or flags per record)");
+    smem_gpu_t* g = b->g;
+    if (!b->g2a_with_ctg || !g->d_ctg_off)
+        return fail(SMEM_E_ARG, "smem_batch_sam: smem_batch_reg2aln ran without a contig table (smem_gpu_load_contigs)");
+    if (!g->d_ctg_names || g->n_ctg_names != g->n_ctg)
+        return fail(SMEM_E_ARG, "smem_batch_sam: no contig names (smem_gpu_load_contig_names)");
+    if (!b->text_set) return fail(SMEM_E_ARG, "smem_batch_sam: no read text (smem_batch_set_read_text)");
+    const char* rg = opt && opt->rg_id ? opt->rg_id : "";
+    const size_t rg_len = strlen(rg);
+    if (rg_len > SAM_RG_MAX) return fail(SMEM_E_ARG, "smem_batch_sam: rg_id of more than 1023 bytes");
+    BatchCall call(b);
+    if (call.rc) return call.rc;
+    b->sam_ran = b->sam_fetched = false;
+    g->sam_used.store(true);  // slots reserved from now on carry the stage's buffers
+    const int n = b->n_reads;
+    const uint64_t n_rec = b->tot_g2a;
+    SamBufs& S = b->sam;
+    if (int rc = sam_bufs_size(S, (uint64_t)n, n_rec)) return rc;
+    HIP_TRY(b->h_sam_ctr.grow(2 + (SAM_RG_MAX + 1) / 8));  // pinned: the copies are asynchronous
+    HIP_TRY(S.text.grow(sam_text_estimate((uint64_t)n, n_rec, b->h_offs.p[n])));
+    smem_sam_stats_t& T = b->sam_stats;
+    T = smem_sam_stats_t{};
+    b->tot_sam = 0;
+    if (n == 0) {
+        INJECT(ST_SAM);
+        HIP_TRY(hipStreamSynchronize(b->st));
+        b->sam_ran = true;
+        return SMEM_OK;
+    }
+    if (rg_len) {
+        std::memcpy(b->h_sam_ctr.p + 2, rg, rg_len);
+        HIP_TRY(hipMemcpyAsync(S.rg.p, b->h_sam_ctr.p + 2, rg_len, hipMemcpyHostToDevice, b->st));
+    }
+    SamPass R;
+    std::memset(&R.P, 0, sizeof(R.P));
+    smem::SamParams& P = R.P;
+    P.codes = b->d_codes.p, P.offs = b->d_offs.p, P.qual = b->text_qual ? S.qual.p : nullptr;
+    P.names = S.names.p, P.name_off = S.name_off.p;
+    P.comments = b->text_comments ? S.comments.p : nullptr, P.comment_off = S.comment_off.p;
+    P.n_reads = (uint32_t)n, P.n_rec = (uint32_t)n_rec;
+    P.rec_off = b->fin.sel_off.p, P.alns = b->g2a.alns.p, P.rid = b->g2a.rid.p;
+    P.idx = b->fin.out_idx.p, P.sel = b->fin.out_sel.p, P.regs = reinterpret_cast<const smem::G2aReg*>(b->fin.out_regs.p);
+    P.fin_status = b->fin.status.p;
+    P.cigar = b->g2a.cigar.p, P.md = b->g2a.md.p;
+    P.ctg_off = g->d_ctg_off, P.ctg_names = g->d_ctg_names, P.ctg_name_off = g->d_ctg_name_off, P.n_ctg = g->n_ctg;
+    P.rg = S.rg.p, P.rg_len = (uint32_t)rg_len;
+    P.rec_len = S.rec_len.p, P.sa_len = S.sa_len.p, P.read_bytes = S.read_bytes.p, P.status = S.status.p;
+    P.text_off = S.text_off.p, P.cnt = S.cnt.p;
+    R.read_bytes = S.read_bytes.p, R.text_off = S.text_off.p, R.scan_tmp = &S.scan_tmp, R.h_ctr = b->h_sam_ctr.p;
+    R.ev = b->ev, R.inject = ST_SAM;
+    if (int rc = run_sam_len(R, b->st)) return rc;
+    const uint64_t total = b->h_sam_ctr.p[0];
+    HIP_TRY(S.text.grow(total));  // (deterministic: the write pass stores exactly the counted bytes)
+    P.text = S.text.p;
+    if (int rc = run_sam_write(R, b->st)) return rc;
+    const uint32_t* cnt = reinterpret_cast<const uint32_t*>(b->h_sam_ctr.p + 1);
+    b->tot_sam = total;
+    T.sam_ms = (double)R.ms_len + (double)R.ms_write, T.sam_write_ms = (double)R.ms_write;
+    T.n_sam_bytes = total, T.n_sam_host = cnt[smem::SAM_N_HOST];
+    b->sam_ran = true;
+    return SMEM_OK;
+}
+
+int smem_batch_sam_results(const smem_batch_t* b, const char** text, const uint64_t** text_off, const int32_t** status,
+                           uint64_t* n_bytes) {
+    if (!b || !b->sam_fetched) return SMEM_E_ARG;
+    if (text) *text = b->h_sam_text.p;
+    if (text_off) *text_off = b->h_sam_off.p;
+    if (status) *status = b->h_sam_status.p;
+    if (n_bytes) *n_bytes = b->tot_sam;
+    return SMEM_OK;
+}
+
+int smem_batch_sam_stats(const smem_batch_t* b, smem_sam_stats_t* st) {
+    if (!b || !st) return SMEM_E_ARG;
+    *st = b->sam_stats;
+    return SMEM_OK;
+}
+
+int smem_sam_text(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_t* offs, const char* names,
+                  const uint64_t* name_off, const char* qual, const char* comments, const uint64_t* comment_off,
+                  const uint64_t* aln_off, const smem_aln_t* alns, const int32_t* rid, const smem_sam_rec_t* recs,
+                  const int32_t* fin_status, const uint32_t* cigar, uint64_t n_cigar_words, const char* md,
+                  uint64_t n_md_bytes, int n_seqs, const int64_t* ctg_offset, const char* ctg_names,
+                  const uint64_t* ctg_name_off, const smem_sam_opt_t* opt, char* text, uint64_t text_cap,
+                  uint64_t* text_off, int32_t* status, uint64_t* n_bytes, double* kernel_ms) {
+    g_err[0] = 0;
+    // every check below is the host's: nothing touches a device before they have passed
+    if (!g || n_reads < 0 || !n_bytes || !text_off || (text_cap > 0 && !text) ||
+        (n_reads > 0 && (!codes || !offs || !names || !name_off || !aln_off || !status)) || (comments && !comment_off))
+        return fail(SMEM_E_ARG, "smem_sam_text: bad arguments");
+    const char* rg = opt && opt->rg_id ? opt->rg_id : "";
+    const size_t rg_len = strlen(rg);
+    if (rg_len > SAM_RG_MAX) return fail(SMEM_E_ARG, "smem_sam_text: rg_id of more than 1023 bytes");
+    if (kernel_ms) *kernel_ms = 0.0;
+    *n_bytes = 0, text_off[0] = 0;
+    if (n_reads == 0) return SMEM_OK;
+    if (aln_off[0] != 0) return fail(SMEM_E_ARG, "smem_sam_text: aln_off must start at 0");
+    for (int r = 0; r < n_reads; ++r) {
+        if (offs[r + 1] < offs[r] || offs[r + 1] - offs[r] > (1u << 30) || aln_off[r + 1] < aln_off[r] ||
+            name_off[r + 1] < name_off[r] || (comments && comment_off[r + 1] < comment_off[r]))
+            return fail(SMEM_E_ARG, "smem_sam_text: offsets not ascending");
+        if (name_off[r + 1] - name_off[r] > (uint64_t)smem::SAM_NAME_MAX)
+            return fail(SMEM_E_ARG, "smem_sam_text: a name of more than 255 bytes");
+    }
+    const uint64_t n_bases = offs[n_reads], n_rec = aln_off[n_reads];
+    if (n_rec >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_sam_text: too many records");
+    if (n_rec > 0 && (!alns || !rid || !recs || n_seqs <= 0 || !ctg_offset || !ctg_names || !ctg_name_off))
+        return fail(SMEM_E_ARG, "smem_sam_text: no record / contig arrays");
+    for (uint64_t k = offs[0]; k < n_bases; ++k)
+        if (codes[k] > 4) return fail(SMEM_E_ARG, "smem_sam_text: query code > 4");
+    if (n_rec > 0)
+        for (int i = 0; i < n_seqs; ++i)
+            if (ctg_name_off[i + 1] < ctg_name_off[i]) return fail(SMEM_E_ARG, "smem_sam_text: ctg_name_off not ascending");
+    for (uint64_t k = 0; k < n_rec; ++k) {
+        const smem_aln_t& A = alns[k];
+        if (A.status != 0) continue;  // the read goes to the host: nothing of the record is read
+        if (rid[k] < 0 || rid[k] >= n_seqs) return fail(SMEM_E_ARG, "smem_sam_text: a record's rid outside the contigs");
+        if (A.n_cigar < 0 || A.md_len < 0 || A.cigar_off > n_cigar_words || (uint64_t)A.n_cigar > n_cigar_words - A.cigar_off ||
+            A.md_off > n_md_bytes || (uint64_t)A.md_len > n_md_bytes - A.md_off || (A.n_cigar > 0 && !cigar) ||
+            (A.md_len > 0 && !md))
+            return fail(SMEM_E_ARG, "smem_sam_text: a record's CIGAR or MD outside the pools");
+    }
+    const uint64_t N = (uint64_t)n_reads + 1, nn = name_off[n_reads], nc = comments ? comment_off[n_reads] : 0;
+    const uint64_t nnc = n_rec ? ctg_name_off[n_seqs] : 0;
+    DevBuf<uint8_t> dcodes, dscan;
+    DevBuf<char> dqual, dnames, dcomm, dmd, dcn, drg, dtext;
+    DevBuf<uint64_t> doffs, dnoff, dcoff, drecoff, dcnoff, dbytes, dtoff;
+    DevBuf<smem::Aln> daln;
+    DevBuf<int32_t> drid, dfst, dstatus;
+    DevBuf<smem::SamRec> drec;
+    DevBuf<uint32_t> dcig, dreclen, dsalen, dcnt;
+    DevBuf<int64_t> dctg;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct Guard {
+        std::function<void()> f;
+        ~Guard() { f(); }
+    } guard{[&] {
+        dcodes.release(); dscan.release(); dqual.release(); dnames.release(); dcomm.release(); dmd.release();
+        dcn.release(); drg.release(); dtext.release(); doffs.release(); dnoff.release(); dcoff.release();
+        drecoff.release(); dcnoff.release(); dbytes.release(); dtoff.release(); daln.release(); drid.release();
+        dfst.release(); dstatus.release(); drec.release(); dcig.release(); dreclen.release(); dsalen.release();
+        dcnt.release(); dctg.release();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }};
+    DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
+    if (call.rc) return call.rc;
+    const hipStream_t st = call.st;
+    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
+    const uint64_t NR = std::max<uint64_t>(n_rec, 1);
+    HIP_TRY(dcodes.ensure(n_bases));
+    HIP_TRY(doffs.ensure(N));
+    HIP_TRY(dnoff.ensure(N));
+    HIP_TRY(dnames.ensure(nn));
+    if (qual) HIP_TRY(dqual.ensure(n_bases));
+    if (comments) {
+        HIP_TRY(dcoff.ensure(N));
+        HIP_TRY(dcomm.ensure(nc));
+    }
+    HIP_TRY(drecoff.ensure(N));
+    HIP_TRY(daln.ensure(NR));
+    HIP_TRY(drid.ensure(NR));
+    HIP_TRY(drec.ensure(NR));
+    if (fin_status) HIP_TRY(dfst.ensure((uint64_t)n_reads));
+    HIP_TRY(dcig.ensure(n_cigar_words));
+    HIP_TRY(dmd.ensure(n_md_bytes));
+    HIP_TRY(dctg.ensure((uint64_t)std::max(n_seqs, 1)));
+    HIP_TRY(dcnoff.ensure((uint64_t)std::max(n_seqs, 1) + 1));
+    HIP_TRY(dcn.ensure(nnc));
+    HIP_TRY(drg.ensure(rg_len));
+    HIP_TRY(dreclen.ensure(NR));
+    HIP_TRY(dsalen.ensure(NR));
+    HIP_TRY(dcnt.ensure(smem::SAM_CNTS));
+    HIP_TRY(dbytes.ensure((uint64_t)n_reads));
+    HIP_TRY(dtoff.ensure(N));
+    HIP_TRY(dstatus.ensure((uint64_t)n_reads));
+    HIP_TRY(dtext.ensure(text_cap));
+    size_t tmp = 0;
+    HIP_TRY(smem_launch_offsets(nullptr, nullptr, n_reads, nullptr, &tmp, nullptr));
+    HIP_TRY(dscan.ensure(tmp + 256));
+    if (n_bases) HIP_TRY(hipMemcpyAsync(dcodes.p, codes, n_bases, hipMemcpyHostToDevice, st));
+    if (qual && n_bases) HIP_TRY(hipMemcpyAsync(dqual.p, qual, n_bases, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(doffs.p, offs, 8 * N, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dnoff.p, name_off, 8 * N, hipMemcpyHostToDevice, st));
+    if (nn) HIP_TRY(hipMemcpyAsync(dnames.p, names, nn, hipMemcpyHostToDevice, st));
+    if (comments) {
+        HIP_TRY(hipMemcpyAsync(dcoff.p, comment_off, 8 * N, hipMemcpyHostToDevice, st));
+        if (nc) HIP_TRY(hipMemcpyAsync(dcomm.p, comments, nc, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipMemcpyAsync(drecoff.p, aln_off, 8 * N, hipMemcpyHostToDevice, st));
+    if (n_rec) {
+        HIP_TRY(hipMemcpyAsync(daln.p, alns, sizeof(smem::Aln) * n_rec, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(drid.p, rid, sizeof(int32_t) * n_rec, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(drec.p, recs, sizeof(smem::SamRec) * n_rec, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dctg.p, ctg_offset, sizeof(int64_t) * (size_t)n_seqs, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dcnoff.p, ctg_name_off, 8 * ((size_t)n_seqs + 1), hipMemcpyHostToDevice, st));
+        if (nnc) HIP_TRY(hipMemcpyAsync(dcn.p, ctg_names, nnc, hipMemcpyHostToDevice, st));
+    }
+    if (fin_status) HIP_TRY(hipMemcpyAsync(dfst.p, fin_status, sizeof(int32_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
+    if (n_cigar_words && cigar) HIP_TRY(hipMemcpyAsync(dcig.p, cigar, 4 * n_cigar_words, hipMemcpyHostToDevice, st));
+    if (n_md_bytes && md) HIP_TRY(hipMemcpyAsync(dmd.p, md, n_md_bytes, hipMemcpyHostToDevice, st));
+    if (rg_len) HIP_TRY(hipMemcpyAsync(drg.p, rg, rg_len, hipMemcpyHostToDevice, st));
+    uint64_t h_ctr[2] = {0, 0};
+    SamPass R;
+    std::memset(&R.P, 0, sizeof(R.P));
+    smem::SamParams& P = R.P;
+    P.codes = dcodes.p, P.offs = doffs.p, P.qual = qual ? dqual.p : nullptr;
+    P.names = dnames.p, P.name_off = dnoff.p, P.comments = comments ? dcomm.p : nullptr, P.comment_off = dcoff.p;
+    P.n_reads = (uint32_t)n_reads, P.n_rec = (uint32_t)n_rec;
+    P.rec_off = drecoff.p, P.alns = daln.p, P.rid = drid.p, P.recs = drec.p;
+    P.fin_status = fin_status ? dfst.p : nullptr;
+    P.cigar = dcig.p, P.md = dmd.p;
+    P.ctg_off = dctg.p, P.ctg_names = dcn.p, P.ctg_name_off = dcnoff.p, P.n_ctg = n_rec ? n_seqs : 0;
+    P.rg = drg.p, P.rg_len = (uint32_t)rg_len;
+    P.rec_len = dreclen.p, P.sa_len = dsalen.p, P.read_bytes = dbytes.p, P.status = dstatus.p;
+    P.text_off = dtoff.p, P.cnt = dcnt.p, P.text = dtext.p;
+    R.read_bytes = dbytes.p, R.text_off = dtoff.p, R.scan_tmp = &dscan, R.h_ctr = h_ctr, R.ev = ev, R.inject = ST_SAM;
+    if (int rc = run_sam_len(R, st)) return rc;
+    if (kernel_ms) *kernel_ms = (double)R.ms_len;
+    *n_bytes = h_ctr[0];
+    HIP_TRY(hipMemcpyAsync(text_off, dtoff.p, 8 * N, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(status, dstatus.p, sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_ctr[0] > text_cap) return fail(SMEM_E_CAPACITY, "smem_sam_text: text buffer too small");
+    if (int rc = run_sam_write(R, st)) return rc;
+    if (kernel_ms) *kernel_ms += (double)R.ms_write;
+    if (h_ctr[0]) HIP_TRY(hipMemcpyAsync(text, dtext.p, h_ctr[0], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return SMEM_OK;
 }
 
@@ -3708,6 +4164,8 @@ static int collect_batch(smem_gpu_t* g, int slot, int n_reads, int max_len, uint
 // both once with a measuring Arena, whose buffers are placeholders)
 static int fin_bufs_size(FinBufs& F, uint64_t n_reads, uint64_t n_regs);
 static int g2a_bufs_size(G2aBufs& G, uint64_t n_rec);
+static int sam_bufs_size(SamBufs& S, uint64_t n_reads, uint64_t n_rec);
+static uint64_t sam_text_estimate(uint64_t n_reads, uint64_t n_rec, uint64_t n_bases);
 static int batch_prealloc(smem_batch_t* b) {
     const uint64_t R = (uint64_t)b->max_reads;
     const uint64_t ni = R * 40, no = R * 16, nc = R * 6, ns = R * 12;
@@ -3746,6 +4204,16 @@ static int batch_prealloc(smem_batch_t* b) {
         HIP_TRY(b->g2a.cigar.grow(R * 2 * 16));
         HIP_TRY(b->g2a.md.grow(R * 2 * 48));
         HIP_TRY(b->h_g2a_ctr.grow(8));
+    }
+    if (b->g->sam_used.load()) {  // ~1.2 records a read, as above
+        if (int rc = sam_bufs_size(b->sam, R, R * 2)) return rc;
+        HIP_TRY(b->sam.text.grow(sam_text_estimate(R, R * 2, b->max_bases)));
+        HIP_TRY(b->h_sam_ctr.grow(2 + 128));
+        // the read text: names at 32 bytes a read, a quality per base (comments come with the first batch that has them)
+        HIP_TRY(b->sam.name_off.grow(R + 1));
+        HIP_TRY(b->sam.names.grow(R * 32));
+        HIP_TRY(b->sam.qual.grow(b->max_bases));
+        HIP_TRY(b->h_sam_stage.grow(16 * (R + 1) + R * 32 + b->max_bases));
     }
     AlnHeavyBufs& H = b->aln_heavy;
     HIP_TRY(H.pre.grow(ns));
@@ -3842,6 +4310,7 @@ static int batch_warmup(smem_batch_t* b) {
         HIP_TRY(smem_preload_chain());
         HIP_TRY(smem_preload_ksw());
         HIP_TRY(smem_preload_aln());
+        HIP_TRY(smem_preload_sam());
         return SMEM_OK;
     }
     if (!g->d_pac || g->l_pac < 4096) return SMEM_OK;

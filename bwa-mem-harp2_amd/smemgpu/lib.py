@@ -42,12 +42,15 @@ EXPORTED = [
     "smem_reg2aln",
     "smem_fin_opt_default", "smem_reg_finalize", "smem_batch_reg_finalize", "smem_batch_fin_results",
     "smem_gpu_load_contigs", "smem_batch_reg2aln", "smem_batch_aln2_results",
+    "smem_gpu_load_contig_names", "smem_batch_set_read_text", "smem_batch_sam", "smem_batch_sam_results",
+    "smem_sam_text", "smem_batch_sam_stats",
 ]
 
 # smem_batch_fetch_mask bits (include/smem_gpu.h)
 FETCH_INTV, FETCH_SA, FETCH_CHAINS, FETCH_REGS, FETCH_ALL = 1, 2, 4, 8, 15
 FETCH_FIN = 16   # Batch.reg_finalize's results; not part of FETCH_ALL
 FETCH_ALN = 32   # Batch.reg2aln's results; not part of FETCH_ALL
+FETCH_SAM = 64   # Batch.sam's text; not part of FETCH_ALL
 COLLECT_NO_FETCH = 1
 
 
@@ -112,6 +115,12 @@ class BatchStats(C.Structure):
                 ("n_fin", C.c_uint64), ("n_fin_sel", C.c_uint64),
                 ("g2a_ms", C.c_double), ("g2a_prep_ms", C.c_double), ("n_g2a", C.c_uint64),
                 ("n_g2a_deferred", C.c_uint64), ("n_g2a_xref", C.c_uint64), ("n_g2a_passes", C.c_uint64)]
+
+
+class SamStats(C.Structure):
+    """smem_sam_stats_t"""
+    _fields_ = [("sam_ms", C.c_double), ("n_sam_bytes", C.c_uint64), ("n_sam_host", C.c_uint64),
+                ("sam_write_ms", C.c_double)]
 
 
 class StreamStats(C.Structure):
@@ -191,6 +200,22 @@ ALN_DT = np.dtype([("pos", "<i8"), ("is_rev", "<i4"), ("n_cigar", "<i4"), ("NM",
                    ("pad", "<i4")])
 ALN_UNMAPPED, ALN_NOCIGAR, ALN_REJECT, ALN_XREF = 1, 2, 3, 4
 FIN_SEL_DT = np.dtype([("mapq", "<i4"), ("flag", "<i4"), ("xs", "<i4")])   # smem_fin_sel_t
+SAM_REC_DT = np.dtype([("mapq", "<i4"), ("flag", "<i4"), ("score", "<i4"), ("xs", "<i4")])   # smem_sam_rec_t
+SAM_HOST = 1     # SMEM_SAM_HOST: the read's lines are the caller's
+
+
+class SamOptT(C.Structure):
+    """smem_sam_opt_t"""
+    _fields_ = [("rg_id", C.c_char_p)]
+
+
+def pack_strings(strs) -> tuple:
+    """[str or bytes] -> (uint8 bytes, uint64 offsets[n + 1]): the layout names and comments travel in"""
+    b = [x if isinstance(x, (bytes, bytearray)) else str(x).encode("latin-1") for x in strs]
+    off = np.zeros(len(b) + 1, dtype=np.uint64)
+    if b:
+        off[1:] = np.cumsum([len(x) for x in b])
+    return np.frombuffer(b"".join(b), dtype=np.uint8).copy(), off
 SMEM_E_CAPACITY = -6
 
 
@@ -249,6 +274,18 @@ def load() -> C.CDLL:
     lib.smem_batch_aln2_results.argtypes = [C.c_void_p, P(C.c_void_p), P(P(C.c_int32)), P(P(C.c_uint64)),
                                             P(P(C.c_uint32)), P(C.c_uint64), P(C.c_void_p), P(C.c_uint64),
                                             P(C.c_uint64)]
+    if hasattr(lib, "smem_sam_text"):  # absent from A/B libraries built before the SAM text stage
+        lib.smem_gpu_load_contig_names.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.smem_batch_set_read_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.smem_batch_sam.argtypes = [C.c_void_p, P(SamOptT)]
+        lib.smem_batch_sam_stats.argtypes = [C.c_void_p, P(SamStats)]
+        lib.smem_batch_sam_results.argtypes = [C.c_void_p, P(C.c_void_p), P(P(C.c_uint64)), P(P(C.c_int32)),
+                                               P(C.c_uint64)]
+        lib.smem_sam_text.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 13 + [C.c_uint64, C.c_void_p, C.c_uint64,
+                                                                                 C.c_int, C.c_void_p, C.c_void_p,
+                                                                                 C.c_void_p, P(SamOptT), C.c_void_p,
+                                                                                 C.c_uint64, C.c_void_p, C.c_void_p,
+                                                                                 P(C.c_uint64), P(C.c_double)]
     lib.smem_chain_opt_default.argtypes = [P(ChainOptT)]
     lib.smem_chain_opt_default.restype = None
     lib.smem_batch_chain.argtypes = [C.c_void_p, C.c_int64, P(ChainOptT)]
@@ -492,6 +529,18 @@ class AlnResults:
 
 
 @dataclass
+class SamResults:
+    """alignments -> SAM text (smem_batch_sam / smem_sam_text)"""
+    text: np.ndarray      # uint8: read r's lines are text[text_off[r] : text_off[r + 1]], reads in batch order
+    text_off: np.ndarray  # (n_reads + 1,) uint64
+    status: np.ndarray    # (n_reads,) int32: 0, or SAM_HOST (no bytes: the caller prints the read)
+    kernel_ms: float = 0.0
+
+    def read(self, r: int) -> bytes:
+        return self.text[int(self.text_off[r]):int(self.text_off[r + 1])].tobytes()
+
+
+@dataclass
 class Results:
     intv: np.ndarray      # (N, 4) uint64: x0, x1, x2, info
     intv_off: np.ndarray  # (n_reads + 1,) uint64
@@ -506,6 +555,7 @@ class Results:
     reg_off: np.ndarray | None = None  # (n_reads + 1,) uint64
     fin: "FinResults | None" = None    # when Batch.reg_finalize() ran and FETCH_FIN was asked for
     aln: "AlnResults | None" = None    # when Batch.reg2aln() ran and FETCH_ALN was asked for
+    sam: "SamResults | None" = None    # when Batch.sam() ran and FETCH_SAM was asked for
 
     def read_chains(self, i: int) -> list:
         """read i's chains as [(pos, seeds)], in mem_chain(+flt) order."""
@@ -763,6 +813,77 @@ class Gpu:
         _check(load().smem_gpu_load_contigs(self._h, offsets.size, offsets.ctypes.data, lens.ctypes.data, int(l_pac)),
                "smem_gpu_load_contigs")
 
+    def load_contig_names(self, names) -> None:
+        """Keep the contigs' names (bns->anns[].name) resident beside the table of
+        load_contigs, one per contig (smem_gpu_load_contig_names): Batch.sam prints them."""
+        data, off = pack_strings(names)
+        _check(load().smem_gpu_load_contig_names(self._h, len(names), data.ctypes.data, off.ctypes.data),
+               "smem_gpu_load_contig_names")
+
+    def sam_text(self, codes, offs, names, quals, comments, aln_off, alns, rid, recs, cigar, md, ctg_offsets, ctg_names,
+                 fin_status=None, rg_id=None, text_cap: int | None = None, grow: bool = True) -> "SamResults":
+        """mem_reg2sam_se's text of every read over host buffers (smem_sam_text): names /
+        comments as lists (comments None: none), quals a uint8 array by offs (None: '*'), alns
+        as ALN_DT with rid (int32) and recs (SAM_REC_DT) per record, aln_off the reads' records,
+        cigar / md the pools alns points into, the contigs' offsets and names.  The text buffer
+        starts at text_cap bytes (default: a guess) and the call is repeated with the size the
+        library reports when it is too small (grow=False: SmemError with .n_bytes instead)."""
+        lib = load()
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = offs.size - 1
+        nm, nm_off = pack_strings(names)
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+            if quals.size < int(offs[-1]):
+                raise SmemError("sam_text: one quality per base")
+        cm = cm_off = None
+        if comments is not None:
+            cm, cm_off = pack_strings(comments)
+        aln_off = np.ascontiguousarray(aln_off, dtype=np.uint64)
+        alns = np.ascontiguousarray(alns, dtype=ALN_DT)
+        rid = np.ascontiguousarray(rid, dtype=np.int32)
+        recs = np.ascontiguousarray(recs, dtype=SAM_REC_DT)
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+        md = np.ascontiguousarray(md, dtype=np.uint8)
+        if len(names) != n or aln_off.size != n + 1 or (comments is not None and len(comments) != n):
+            raise SmemError("sam_text: one name (and comment) per read, aln_off of n_reads + 1 entries")
+        n_rec = int(aln_off[-1]) if n >= 0 and aln_off.size else 0
+        if alns.size < n_rec or rid.size < n_rec or recs.size < n_rec:
+            raise SmemError("sam_text: aln_off ends past the records")
+        ctg_offsets = np.ascontiguousarray(ctg_offsets, dtype=np.int64)
+        cn, cn_off = pack_strings(ctg_names)
+        if len(ctg_names) != ctg_offsets.size:
+            raise SmemError("sam_text: one name per contig")
+        if fin_status is not None:
+            fin_status = np.ascontiguousarray(fin_status, dtype=np.int32)
+            if fin_status.size != n:
+                raise SmemError("sam_text: one finalize status per read")
+        opt = SamOptT(rg_id.encode("latin-1") if rg_id else None)
+        cap = int(text_cap) if text_cap is not None else 2 * int(offs[-1]) + 160 * (n_rec + n) + 256
+        text_off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ms, nb = C.c_double(), C.c_uint64()
+
+        def ptr(a):
+            return a.ctypes.data if a is not None else None
+        while True:
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = lib.smem_sam_text(self._h, n, ptr(codes), ptr(offs), ptr(nm), ptr(nm_off), ptr(quals), ptr(cm),
+                                   ptr(cm_off), ptr(aln_off), ptr(alns), ptr(rid), ptr(recs), ptr(fin_status),
+                                   ptr(cigar), cigar.size, ptr(md), md.size, ctg_offsets.size, ptr(ctg_offsets), ptr(cn),
+                                   ptr(cn_off), C.byref(opt), ptr(text), cap, ptr(text_off), ptr(status), C.byref(nb),
+                                   C.byref(ms))
+            if rc == SMEM_E_CAPACITY and nb.value > cap and grow:
+                cap = int(nb.value)
+                continue
+            if rc == SMEM_E_CAPACITY:
+                err = SmemError(f"smem_sam_text failed: SMEM_E_CAPACITY: the text needs {nb.value} bytes")
+                err.n_bytes = int(nb.value)
+                raise err
+            _check(rc, "smem_sam_text")
+            return SamResults(text[:int(nb.value)], text_off, status[:n], ms.value)
+
     def chain2aln(self, pac, l_pac: int, codes, offs, chains, chain_off, seeds, opt) -> tuple:
         """mem_chain2aln_short / mem_chain2aln of every chain of every read
         (software/bwamem.c:1452-1460) on this device.  opt is a ctypes struct
@@ -915,7 +1036,12 @@ class Batch:
     def stats(self) -> dict:
         s = BatchStats()
         _check(load().smem_batch_stats(self._h, C.byref(s)), "smem_batch_stats")
-        return {k: getattr(s, k) for k, _ in BatchStats._fields_}
+        out = {k: getattr(s, k) for k, _ in BatchStats._fields_}
+        if hasattr(load(), "smem_batch_sam_stats"):  # Batch.sam's, from their own struct (smem_batch_sam_stats)
+            t = SamStats()
+            _check(load().smem_batch_sam_stats(self._h, C.byref(t)), "smem_batch_sam_stats")
+            out.update({k: getattr(t, k) for k, _ in SamStats._fields_})
+        return out
 
     def sa(self, min_seed_len: int = 19, max_occ: int = 10000) -> None:
         """bwt_sa of every seed occurrence of the last run (smem_batch_sa)."""
@@ -963,6 +1089,35 @@ class Batch:
                 raise SmemError("reg2aln: idx_off must have n_reads + 1 entries and end at idx.size")
             pi, po = idx.ctypes.data, idx_off.ctypes.data
         _check(load().smem_batch_reg2aln(self._h, C.byref(opt), pi, po), "smem_batch_reg2aln")
+
+    def set_read_text(self, names, quals=None, comments=None) -> None:
+        """The names (one per read, at most 255 bytes), qualities (a uint8 array over all
+        reads in batch order, or None: '*') and comments (a list, or None) Batch.sam prints
+        (smem_batch_set_read_text); a later set_reads ends them."""
+        n = self.n_reads
+        if len(names) != n or (comments is not None and len(comments) != n):
+            raise SmemError("set_read_text: one name (and comment) per read")
+        nm, nm_off = pack_strings(names)
+        q = None
+        if quals is not None:
+            q = np.ascontiguousarray(quals, dtype=np.uint8)
+            if q.size != int(self._keep[1][-1] - self._keep[1][0]):
+                raise SmemError("set_read_text: one quality per base")
+        cm = cm_off = None
+        if comments is not None:
+            cm, cm_off = pack_strings(comments)
+        _check(load().smem_batch_set_read_text(self._h, nm.ctypes.data, nm_off.ctypes.data,
+                                               q.ctypes.data if q is not None else None,
+                                               cm.ctypes.data if cm is not None else None,
+                                               cm_off.ctypes.data if cm_off is not None else None),
+               "smem_batch_set_read_text")
+
+    def sam(self, rg_id=None) -> None:
+        """mem_reg2sam_se's text of every read of the last reg2aln() (the stage's own
+        selection, with a contig table and names, after set_read_text), in HBM
+        (smem_batch_sam); fetch(FETCH_SAM) returns it as .sam."""
+        opt = SamOptT(rg_id.encode("latin-1") if rg_id else None)
+        _check(load().smem_batch_sam(self._h, C.byref(opt)), "smem_batch_sam")
 
     def debug_words(self, n_words: int) -> np.ndarray:
         out = np.zeros(n_words, dtype=np.uint64)
@@ -1037,6 +1192,13 @@ class Batch:
                 np.ctypeslib.as_array(ao, shape=(n + 1,)).copy(),
                 np.ctypeslib.as_array(cg, shape=(max(kc, 1),))[:kc].copy(),
                 np.frombuffer((C.c_char * max(km, 1)).from_address(mdp.value), dtype=np.uint8)[:km].copy())
+        tx, to, ts, tb = C.c_void_p(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_int32)(), C.c_uint64()
+        if lib.smem_batch_sam_results(self._h, C.byref(tx), C.byref(to), C.byref(ts), C.byref(tb)) == 0:
+            k = int(tb.value)
+            res.sam = SamResults(
+                np.frombuffer((C.c_char * max(k, 1)).from_address(tx.value), dtype=np.uint8)[:k].copy(),
+                np.ctypeslib.as_array(to, shape=(n + 1,)).copy(),
+                np.ctypeslib.as_array(ts, shape=(max(n, 1),))[:n].copy(), self.stats()["sam_ms"])
         return res
 
     def close(self) -> None:

@@ -28,7 +28,7 @@
  * caller that takes its CPU path on SMEM_E_DEVICE computes exactly what the
  * reference computes.  Allocation failures are SMEM_E_NOMEM and leave the
  * device usable.  SMEM_GPU_FAIL=<stage>:<k>[:sticky] (stage: upload, seed,
- * sa, chain, aln, fin, g2a, fetch, any) injects SMEM_E_DEVICE into every k-th
+ * sa, chain, aln, fin, g2a, sam, fetch, any) injects SMEM_E_DEVICE into every k-th
  * call of the stage after its work is enqueued, to test that contract.
  */
 #ifndef SMEM_GPU_H
@@ -309,6 +309,7 @@ int  smem_batch_fetch(smem_batch_t *b);
 #define SMEM_FETCH_ALL    15
 #define SMEM_FETCH_FIN    16   /* smem_batch_reg_finalize's results (smem_batch_fin_results); not part of ALL */
 #define SMEM_FETCH_ALN    32   /* smem_batch_reg2aln's results (smem_batch_aln2_results); not part of ALL */
+#define SMEM_FETCH_SAM    64   /* smem_batch_sam's text (smem_batch_sam_results); not part of ALL */
 int  smem_batch_fetch_mask(smem_batch_t *b, int mask);
 /* per-read view of fetched results: the concatenation of all smem_next2
  * lists in order (n_intv intervals) and the size of each list (n_calls) */
@@ -624,6 +625,75 @@ int  smem_batch_reg_finalize(smem_batch_t *b, const int64_t *ids, int64_t id0, c
 int  smem_batch_fin_results(const smem_batch_t *b, const smem_alnreg_t **regs_out, const uint64_t **out_off,
                             const smem_fin_sel_t **sel, const uint64_t **sel_idx, const uint64_t **sel_off,
                             const int32_t **status, uint64_t *n_out, uint64_t *n_sel);
+
+/* ------------------------------------------- alignments -> SAM text */
+/* The text mem_reg2sam_se(opt, bns, pac, s, a, 0, 0) leaves in s->sam (software/bwamem.c:1359-1393,
+ * through mem_aln2sam, :1214-1327) for every read, on the GPU: single end, no mate, no XA; one
+ * line per record of the read's list in list order (SA:Z from the read's own records, hard clips
+ * and a trimmed SEQ / QUAL on every record after the first), or the unmapped line (flag 4,
+ * AS:i:0, XS:i:0) for a read without a record.  No @ header lines. */
+#define SMEM_SAM_HOST 1
+/* status of a read the stage leaves to the caller, the reference's reject -> CPU convention: one
+ * of its records has a status other than 0 (SMEM_ALN_XREF, _REJECT, _NOCIGAR, _UNMAPPED) or
+ * mapq -1, its finalize status is SMEM_FIN_REJECT, or its length is 0.  The read gets zero bytes
+ * (all of its lines: the SA:Z of its other records would need the missing alignment). */
+typedef struct {
+	const char *rg_id;       /* bwa_rg_id: NULL or "": no RG:Z tag (at most 1023 bytes) */
+} smem_sam_opt_t;
+/* what mem_reg2sam_se decides about a record beside its alignment: finalize's capped mapq and
+ * flag (0x100, 0x800, 0x10000; 0x10 comes from the alignment's strand), the final region's
+ * score (AS) and xs (XS; -1: none) */
+typedef struct { int32_t mapq, flag, score, xs; } smem_sam_rec_t;
+/* bns->anns[].name beside the table of smem_gpu_load_contigs: name i is names[name_off[i] ..
+ * name_off[i + 1]).  SMEM_E_ARG unless a contig table of the same n_seqs is loaded.  Loading
+ * again replaces the names; loading another contig table drops them; freed at shutdown. */
+int  smem_gpu_load_contig_names(smem_gpu_t *gpu, int n_seqs, const char *names, const uint64_t *name_off);
+/* The text of the batch's reads (after smem_batch_set_reads*): read r's name is names[name_off[r]
+ * .. name_off[r + 1]), at most 255 bytes (more: SMEM_E_ARG); qual (NULL: the stage prints '*')
+ * holds the reads' qualities one after the other in batch order, as the codes were given;
+ * comments / comment_off (NULL: none; an empty comment: none) as the names.  Copied through
+ * pinned batch memory.  A later smem_batch_set_reads* ends them. */
+int  smem_batch_set_read_text(smem_batch_t *b, const char *names, const uint64_t *name_off, const char *qual,
+                              const char *comments, const uint64_t *comment_off);
+/* After smem_batch_reg2aln (idx == NULL: only the finalize selection has MAPQ and flags per record)
+ * with a contig table, contig names and read text: every read's lines, in HBM.  Two passes with
+ * one 8-byte total read in between: the lengths (per record, per read, the offset scan), then
+ * the text; the text buffer grows to the total when it is too small, so the caller never sees
+ * SMEM_E_CAPACITY.  SMEM_E_ARG when one of the above is missing.  smem_batch_fetch_mask(b,
+ * SMEM_FETCH_SAM) copies the results; smem_batch_sam_results returns them (any pointer may be
+ * NULL): text[text_off[r] .. text_off[r + 1]) are read r's lines, reads in batch order (a batch
+ * whose reads all have status 0 can be written to a file as it is), status[r] is 0 or
+ * SMEM_SAM_HOST.  A later smem_batch_chain2aln, _reg_finalize or _reg2aln ends the results. */
+int  smem_batch_sam(smem_batch_t *b, const smem_sam_opt_t *opt);
+int  smem_batch_sam_results(const smem_batch_t *b, const char **text, const uint64_t **text_off,
+                            const int32_t **status, uint64_t *n_bytes);
+/* The stage's statistics of the batch's last smem_batch_sam (zero before it).  They have a
+ * struct of their own: smem_batch_stats_t keeps its size and every member its place. */
+typedef struct {
+	double sam_ms;           /* the length pass (with its scan) + the write pass, HIP events */
+	uint64_t n_sam_bytes;    /* bytes of text written */
+	uint64_t n_sam_host;     /* reads left to the caller (SMEM_SAM_HOST) */
+	double sam_write_ms;     /* the write pass alone (tools/samtext_time.py: its bytes per second) */
+} smem_sam_stats_t;
+int  smem_batch_sam_stats(const smem_batch_t *b, smem_sam_stats_t *st);
+/* The same over host buffers.  Reads: codes (0..4) / offs[n_reads + 1], names / name_off, qual
+ * (by offs; NULL: '*'), comments / comment_off (NULL: none).  Records: read r's are
+ * [aln_off[r], aln_off[r + 1]) (aln_off[0] == 0), each an smem_aln_t with its CIGAR / MD in the
+ * pools (smem_reg2aln's or smem_batch_aln2_results' layout; pos in concatenated coordinates), its
+ * contig rid and an smem_sam_rec_t; fin_status (NULL: all 0) per read.  Contigs: offset[n_seqs]
+ * and names by ctg_name_off[n_seqs + 1].  text (text_cap bytes), text_off[n_reads + 1] and
+ * status[n_reads] are filled; *n_bytes gets the text's size.  SMEM_E_CAPACITY when text_cap is
+ * too small: *n_bytes (and text_off, status) then give what a retry needs.  kernel_ms (may be
+ * NULL): both passes.  Arguments are checked on the host before any device is touched:
+ * SMEM_E_ARG for gpu == NULL, offsets that do not ascend, a name over 255 bytes, a code above 4,
+ * and a record of status 0 whose rid, CIGAR or MD lies outside what was passed. */
+int  smem_sam_text(smem_gpu_t *gpu, int n_reads, const uint8_t *codes, const uint64_t *offs, const char *names,
+                   const uint64_t *name_off, const char *qual, const char *comments, const uint64_t *comment_off,
+                   const uint64_t *aln_off, const smem_aln_t *alns, const int32_t *rid, const smem_sam_rec_t *recs,
+                   const int32_t *fin_status, const uint32_t *cigar, uint64_t n_cigar_words, const char *md,
+                   uint64_t n_md_bytes, int n_seqs, const int64_t *ctg_offset, const char *ctg_names,
+                   const uint64_t *ctg_name_off, const smem_sam_opt_t *opt, char *text, uint64_t text_cap,
+                   uint64_t *text_off, int32_t *status, uint64_t *n_bytes, double *kernel_ms);
 
 /* ---------------------------------------------------------- telemetry */
 typedef struct {
