@@ -173,11 +173,18 @@ static bool guard_on() {
     return on;
 }
 
+// DevBuf / HostBuf own their memory: what a scope declares is released when the scope ends (a
+// one-shot entry point declares its buffers before its DeviceCall, so the call has drained its
+// streams by then); a batch's are released one by one in smem_batch_destroy, which times them
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
     bool own = true;  // false: carved from the slot's block
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t want) {
         if (want <= n && p) return hipSuccess;
         release();
@@ -214,6 +221,10 @@ struct HostBuf {
     T* p = nullptr;
     size_t n = 0;
     bool own = true;
+    HostBuf() = default;
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    ~HostBuf() { release(); }
     // a pinned result buffer of at least `want` elements, grown with 25 %
     // headroom: batches of a worker vary in size, and re-pinning on every
     // slightly larger one costs more than the copy
@@ -243,12 +254,35 @@ struct HostBuf {
     uint64_t bytes() const { return p ? (uint64_t)n * sizeof(T) : 0; }
 };
 
+// the events of a one-shot entry point, created on its way and destroyed when its scope ends
+// (declared with its buffers, before the DeviceCall)
+template <int N>
+struct Events {
+    hipEvent_t e[N] = {};
+    Events() = default;
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+    ~Events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    hipError_t create() {
+        for (hipEvent_t& x : e)
+            if (hipError_t r = hipEventCreate(&x)) return r;
+        return hipSuccess;
+    }
+    hipEvent_t& operator[](int k) { return e[k]; }
+};
+
 }  // namespace
 
 extern "C" hipError_t smem_preload_seed(void);
 extern "C" hipError_t smem_preload_chain(void);
 extern "C" hipError_t smem_preload_ksw(void);
 extern "C" hipError_t smem_preload_aln(void);
+
+// the runtime's own types: hidden, so their constructors and destructors are not exported
+#pragma GCC visibility push(hidden)
 
 // device SA sampling interval = 2^SA_DENSE_SHIFT (see smem_gpu_load_sa)
 constexpr uint32_t SA_DENSE_SHIFT = 2;
@@ -399,6 +433,24 @@ static void gpu_wait(smem_gpu_t* g) {
     if (f.valid()) f.wait();
 }
 
+// A batch's progress through its stages, in the order they feed each other: a stage needs its
+// predecessor's results (stage >= predecessor), and running it again ends every later stage's.
+enum Stage {
+    STAGE_NONE,
+    STAGE_READS,    // smem_batch_set_reads*
+    STAGE_SEEDED,   // smem_batch_run
+    STAGE_SA,       // smem_batch_sa
+    STAGE_CHAINED,  // smem_batch_chain
+    STAGE_REGIONS,  // smem_batch_chain2aln
+    STAGE_FINAL,    // smem_batch_reg_finalize
+    STAGE_ALIGNED,  // smem_batch_reg2aln
+    STAGE_SAMTEXT,  // smem_batch_sam
+};
+// the SMEM_FETCH_* bit of each stage's output
+constexpr int k_stage_fetch[] = {0, 0, SMEM_FETCH_INTV, SMEM_FETCH_SA, SMEM_FETCH_CHAINS, SMEM_FETCH_REGS,
+                                 SMEM_FETCH_FIN, SMEM_FETCH_ALN, SMEM_FETCH_SAM};
+constexpr int k_fetch_any = SMEM_FETCH_ALL | SMEM_FETCH_FIN | SMEM_FETCH_ALN | SMEM_FETCH_SAM;
+
 // scratch of the heavy-read path of chains -> regions
 struct AlnHeavyBufs {
     DevBuf<int32_t> heavy, heavy2;
@@ -425,7 +477,7 @@ struct AlnHeavyBufs {
     DevBuf<int64_t> chmax, crb, cre;
     DevBuf<uint8_t> cmade, ctmp;
     DevBuf<uint2> crng;
-    // f(buf) for every buffer (release, sizes)
+    // f(buf) for every buffer
     template <class F>
     void each(F&& f) {
         f(ckey); f(ckey2); f(coff); f(ccnt); f(cval); f(cval2); f(cq); f(cpos_s); f(cpos_c); f(chord); f(chmax);
@@ -433,9 +485,6 @@ struct AlnHeavyBufs {
         f(gctr); f(gtorder); f(glq); f(chord_g); f(gtasks); f(ccnt_g); f(coff_g); f(ctmp_g); f(hcnt); f(hoff); f(hscnt); f(span); f(ht); f(rnext);
         f(pre); f(pre_short); f(loc); f(short_ok); f(pre_ok); f(tmp); f(tasks); f(torder); f(lq); f(tfail); f(sdec);
         f(chain_read); f(swlist); f(htasks); f(htorder); f(hlq); f(htfail);
-    }
-    void release() {
-        each([](auto& x) { x.release(); });
     }
 };
 
@@ -453,9 +502,6 @@ struct FinBufs {
         f(ctr); f(lane_list); f(wave_list); f(tmp_idx); f(n_out); f(n_sel); f(out_off); f(sel_off); f(out_idx);
         f(status); f(tmp_regs); f(out_regs); f(tmp_sel); f(out_sel); f(scan_tmp); f(ids);
     }
-    void release() {
-        each([](auto& x) { x.release(); });
-    }
 };
 
 // device buffers of regions -> alignments (csrc/global_kernels.h G2aPrepParams / G2aParams)
@@ -472,9 +518,6 @@ struct G2aBufs {
     void each(F&& f) {
         f(task); f(list); f(cnt); f(cigar); f(cur); f(alns); f(rid); f(md); f(scratch); f(idx); f(idx_off);
     }
-    void release() {
-        each([](auto& x) { x.release(); });
-    }
 };
 
 // device buffers of alignments -> SAM text (csrc/sam_kernels.h SamParams); names .. rg: the
@@ -490,9 +533,6 @@ struct SamBufs {
         f(names); f(qual); f(comments); f(rg); f(text); f(name_off); f(comment_off); f(read_bytes); f(text_off);
         f(rec_len); f(sa_len); f(cnt); f(status); f(scan_tmp);
     }
-    void release() {
-        each([](auto& x) { x.release(); });
-    }
 };
 
 struct smem_batch {
@@ -507,6 +547,10 @@ struct smem_batch {
     hipStream_t st2 = nullptr;
     hipStream_t st3 = nullptr;  // chains -> regions: the giant reads' passes and walk (ev_giant joins them)
     hipEvent_t ev_join = nullptr, ev_fork = nullptr, ev_giant = nullptr;
+    // the last stage whose results stand on the device (stage_begin / stage_done) and the
+    // SMEM_FETCH_* outputs whose pinned copies the result accessors may hand out
+    Stage stage = STAGE_NONE;
+    int fetched = 0;
     int max_reads = 0, max_len = 0;
     int read_len_max = 0;  // the longest read of the reads set (set_reads*)
     uint64_t max_bases = 0;
@@ -544,13 +588,11 @@ struct smem_batch {
     HostBuf<Intv> h_intv;
     HostBuf<uint32_t> h_calls;
     HostBuf<uint64_t> h_intv_off, h_call_off;
-    bool fetched = false, ran = false;
     uint64_t tot_intv = 0, tot_calls = 0;
     // bwt_sa of the seed occurrences (smem_batch_sa)
     DevBuf<uint64_t> d_occ_n, d_occ_off, d_sa_pos, d_kstart;
     DevBuf<uint8_t> d_sa_tmp;
     HostBuf<uint64_t> h_occ_off, h_sa_pos;
-    bool sa_ran = false, sa_fetched = false;
     uint64_t tot_occ = 0;
     int sa_min_seed_len = 0;
     // chains (smem_batch_chain)
@@ -565,7 +607,7 @@ struct smem_batch {
     HostBuf<uint64_t> h_chain_off;
     HostBuf<smem::OutChain> h_out_chain;
     HostBuf<smem::SeedRec> h_out_seed;
-    bool chain_ran = false, chain_fetched = false, chain_filtered = false;
+    bool chain_filtered = false;
     uint64_t tot_chains = 0, tot_seeds = 0;
     // alignment regions (smem_batch_chain2aln)
     DevBuf<uint64_t> d_aln_srt, d_aln_nregs, d_aln_regoff;
@@ -574,7 +616,6 @@ struct smem_batch {
     AlnHeavyBufs aln_heavy;     // the heavy-read path's scratch
     HostBuf<uint64_t> h_aln_regoff;
     HostBuf<smem::AlnReg> h_aln_regs;
-    bool aln_ran = false, aln_fetched = false;
     uint64_t tot_regs = 0;
     // final regions (smem_batch_reg_finalize): nothing here is allocated until the stage is called
     FinBufs fin;
@@ -583,7 +624,6 @@ struct smem_batch {
     HostBuf<smem::AlnReg> h_fin_regs;
     HostBuf<smem::FinSel> h_fin_sel;
     HostBuf<int32_t> h_fin_status;
-    bool fin_ran = false, fin_fetched = false;
     uint64_t tot_fin = 0, tot_fin_sel = 0;
     // alignments (smem_batch_reg2aln): nothing here is allocated until the stage is called
     G2aBufs g2a;
@@ -594,7 +634,7 @@ struct smem_batch {
     HostBuf<int32_t> h_g2a_rid;
     HostBuf<uint32_t> h_g2a_cigar;
     HostBuf<char> h_g2a_md;
-    bool g2a_ran = false, g2a_fetched = false, g2a_own_idx = false;
+    bool g2a_own_idx = false;
     uint64_t tot_g2a = 0, tot_g2a_cigar = 0, tot_g2a_md = 0;
     bool g2a_with_ctg = false;                // the last smem_batch_reg2aln looked its records up in the contig table
     // SAM text (smem_batch_set_read_text, smem_batch_sam): nothing here is allocated until they are called
@@ -605,11 +645,26 @@ struct smem_batch {
     HostBuf<uint64_t> h_sam_off;              // text_off[n + 1]
     HostBuf<int32_t> h_sam_status;
     bool text_set = false, text_qual = false, text_comments = false;
-    bool sam_ran = false, sam_fetched = false;
     uint64_t tot_sam = 0;
     smem_sam_stats_t sam_stats{};
     smem_batch_stats_t stats{};
 };
+
+// the top of stage s, after its argument checks: the batch is back at s's predecessor (or where it
+// was, if earlier), and the fetched views of s and of every later stage end; a failure from here on
+// leaves it there
+static void stage_begin(smem_batch_t* b, Stage s) {
+    if (b->stage >= s) b->stage = (Stage)(s - 1);
+    for (int k = s; k <= STAGE_SAMTEXT; ++k) b->fetched &= ~k_stage_fetch[k];
+}
+// stage s succeeded
+static void stage_done(smem_batch_t* b, Stage s) { b->stage = s; }
+// the SMEM_FETCH_* outputs of the stages that have run
+static int stage_outputs(const smem_batch_t* b) {
+    int m = 0;
+    for (int k = STAGE_SEEDED; k <= b->stage; ++k) m |= k_stage_fetch[k];
+    return m;
+}
 
 // d(buf) for every device buffer of a batch, h(buf) for every pinned host one
 template <class D, class H>
@@ -652,8 +707,8 @@ static void guard_check(smem_batch_t* b, hipStream_t st, hipStream_t st2, hipStr
                 if (bad) {
                     fprintf(stderr, "[smem guard] batch %p (max_reads %d, max_len %d, ran %d/%d/%d/%d): buffer #%d of "
                             "%zu x %zu B written past its end: %zu guard bytes, the first at +%zu\n",
-                            (void*)b, b->max_reads, b->max_len, (int)b->ran, (int)b->sa_ran, (int)b->chain_ran,
-                            (int)b->aln_ran, k, x.n, sizeof(*x.p), bad, first);
+                            (void*)b, b->max_reads, b->max_len, (int)(b->stage >= STAGE_SEEDED), (int)(b->stage >= STAGE_SA),
+                            (int)(b->stage >= STAGE_CHAINED), (int)(b->stage >= STAGE_REGIONS), k, x.n, sizeof(*x.p), bad, first);
                     (void)hipMemset(const_cast<char*>(tail), 0xA5, GUARD_BYTES);
                 }
             }
@@ -776,6 +831,8 @@ struct BatchCall : DeviceCall {
         b->st = b->st2 = b->st3 = nullptr;
     }
 };
+
+#pragma GCC visibility pop
 
 extern "C" {
 
@@ -1256,8 +1313,8 @@ static int upload_reads(smem_batch_t* b, int n_reads) {
     int ml = 0;
     for (int i = 0; i < n_reads; ++i) ml = std::max<int>(ml, (int)(b->h_offs.p[i + 1] - b->h_offs.p[i]));
     b->read_len_max = ml;
-    b->ran = b->fetched = false;
-    b->text_set = b->sam_ran = b->sam_fetched = false;  // the read text belongs to the reads it came with
+    stage_begin(b, STAGE_READS);
+    b->text_set = false;  // the read text belongs to the reads it came with
     b->n_reads = 0;
     const uint64_t nb = b->h_offs.p[n_reads];
     HIP_TRY(hipMemcpyAsync(b->d_codes.p, b->h_codes.p, std::max<uint64_t>(nb, 1), hipMemcpyHostToDevice, b->st));
@@ -1265,6 +1322,7 @@ static int upload_reads(smem_batch_t* b, int n_reads) {
     INJECT(ST_UPLOAD);
     HIP_TRY(hipStreamSynchronize(b->st));
     b->n_reads = n_reads;
+    stage_done(b, STAGE_READS);
     return SMEM_OK;
 }
 
@@ -1338,14 +1396,9 @@ static void fill_params(smem_batch_t* b, const smem_opt_t* o, smem::SeedParams& 
 static int batch_run_impl(smem_batch_t* b, const smem_opt_t* opt) {
     smem_gpu_t* g = b->g;
     const int n = b->n_reads;
-    b->fetched = false;
-    b->sa_ran = false;
-    b->sa_fetched = false;
+    stage_begin(b, STAGE_SEEDED);
     b->tot_occ = 0;
-    b->chain_ran = b->chain_fetched = false;
     b->tot_chains = b->tot_seeds = 0;
-    b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
     b->tot_regs = 0;
     b->stats = smem_batch_stats_t{};
     b->stats.block = 256;
@@ -1466,7 +1519,7 @@ static int batch_run_impl(smem_batch_t* b, const smem_opt_t* opt) {
         b->stats.t_start = n > 0 ? ~sp[0] : 0;
         b->stats.t_end = n > 0 ? sp[1] : 0;
     }
-    b->ran = true;
+    stage_done(b, STAGE_SEEDED);
     return SMEM_OK;
 }
 
@@ -1483,14 +1536,12 @@ static int fetch_impl(smem_batch_t* b, int mask) {
     BatchCall call(b);
     if (call.rc) return call.rc;
     // views of an earlier fetch end here (its buffers may be regrown below)
-    b->fetched = b->sa_fetched = b->chain_fetched = b->aln_fetched = b->fin_fetched = b->g2a_fetched = false;
-    b->sam_fetched = false;
+    b->fetched = 0;
+    mask &= stage_outputs(b);
     const int n = b->n_reads;
-    const bool f_intv = mask & SMEM_FETCH_INTV, f_sa = (mask & SMEM_FETCH_SA) && b->sa_ran;
-    const bool f_chain = (mask & SMEM_FETCH_CHAINS) && b->chain_ran, f_aln = (mask & SMEM_FETCH_REGS) && b->aln_ran;
-    const bool f_fin = (mask & SMEM_FETCH_FIN) && b->fin_ran;
-    const bool f_g2a = (mask & SMEM_FETCH_ALN) && b->g2a_ran;
-    const bool f_sam = (mask & SMEM_FETCH_SAM) && b->sam_ran;
+    const bool f_intv = mask & SMEM_FETCH_INTV, f_sa = mask & SMEM_FETCH_SA, f_chain = mask & SMEM_FETCH_CHAINS;
+    const bool f_aln = mask & SMEM_FETCH_REGS, f_fin = mask & SMEM_FETCH_FIN, f_g2a = mask & SMEM_FETCH_ALN;
+    const bool f_sam = mask & SMEM_FETCH_SAM;
     // pinned result buffers grow with headroom: a streamed batch whose next
     // chunk holds a few more intervals must not re-pin a gigabyte
     if (!f_intv) {
@@ -1517,122 +1568,82 @@ static int fetch_impl(smem_batch_t* b, int mask) {
     }
     if (f_intv && b->tot_calls)
         HIP_TRY(hipMemcpyAsync(b->h_calls.p, b->d_flat_calls.p, sizeof(uint32_t) * b->tot_calls, hipMemcpyDeviceToHost, b->st));
+    // the later stages' arrays: the pinned buffer grown to `cnt` elements, then the copy (none of nothing)
+    auto pull = [b](auto& h, const void* d, uint64_t cnt) -> int {
+        HIP_TRY(h.grow(cnt));
+        if (cnt) HIP_TRY(hipMemcpyAsync(h.p, d, sizeof(*h.p) * cnt, hipMemcpyDeviceToHost, b->st));
+        return SMEM_OK;
+    };
+    int r = SMEM_OK;
     if (f_sa) {
-        HIP_TRY(b->h_occ_off.grow(b->tot_intv + 1));
-        HIP_TRY(b->h_sa_pos.grow(b->tot_occ));
-        HIP_TRY(hipMemcpyAsync(b->h_occ_off.p, b->d_occ_off.p, sizeof(uint64_t) * (b->tot_intv + 1),
-                               hipMemcpyDeviceToHost, b->st));
-        if (b->tot_occ)
-            HIP_TRY(hipMemcpyAsync(b->h_sa_pos.p, b->d_sa_pos.p, sizeof(uint64_t) * b->tot_occ, hipMemcpyDeviceToHost,
-                                   b->st));
+        r = pull(b->h_occ_off, b->d_occ_off.p, b->tot_intv + 1);
+        if (!r) r = pull(b->h_sa_pos, b->d_sa_pos.p, b->tot_occ);
     }
-    if (f_chain) {
-        HIP_TRY(b->h_chain_off.grow((uint64_t)n + 1));
-        HIP_TRY(b->h_out_chain.grow(b->tot_chains));
-        HIP_TRY(b->h_out_seed.grow(b->tot_seeds));
-        HIP_TRY(hipMemcpyAsync(b->h_chain_off.p, b->d_chain_off.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost,
-                               b->st));
-        if (b->tot_chains)
-            HIP_TRY(hipMemcpyAsync(b->h_out_chain.p, b->d_out_chain.p, sizeof(smem::OutChain) * b->tot_chains,
-                                   hipMemcpyDeviceToHost, b->st));
-        if (b->tot_seeds)
-            HIP_TRY(hipMemcpyAsync(b->h_out_seed.p, b->d_out_seed.p, sizeof(smem::SeedRec) * b->tot_seeds,
-                                   hipMemcpyDeviceToHost, b->st));
+    if (!r && f_chain) {
+        r = pull(b->h_chain_off, b->d_chain_off.p, (uint64_t)n + 1);
+        if (!r) r = pull(b->h_out_chain, b->d_out_chain.p, b->tot_chains);
+        if (!r) r = pull(b->h_out_seed, b->d_out_seed.p, b->tot_seeds);
     }
-    if (f_aln) {
-        HIP_TRY(b->h_aln_regoff.grow((uint64_t)n + 1));
-        HIP_TRY(b->h_aln_regs.grow(b->tot_regs));
-        HIP_TRY(hipMemcpyAsync(b->h_aln_regoff.p, b->d_aln_regoff.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost,
-                               b->st));
-        if (b->tot_regs)
-            HIP_TRY(hipMemcpyAsync(b->h_aln_regs.p, b->d_aln_out.p, sizeof(smem::AlnReg) * b->tot_regs,
-                                   hipMemcpyDeviceToHost, b->st));
+    if (!r && f_aln) {
+        r = pull(b->h_aln_regoff, b->d_aln_regoff.p, (uint64_t)n + 1);
+        if (!r) r = pull(b->h_aln_regs, b->d_aln_out.p, b->tot_regs);
     }
+    if (r) return r;
     if (f_fin) {
+        // one buffer for both offset arrays: out_off[n + 1], then sel_off[n + 1]
         HIP_TRY(b->h_fin_off.grow(2 * ((uint64_t)n + 1)));
-        HIP_TRY(b->h_fin_status.grow((uint64_t)std::max(n, 1)));
-        HIP_TRY(b->h_fin_regs.grow(b->tot_fin));
-        HIP_TRY(b->h_fin_sel.grow(b->tot_fin));
-        HIP_TRY(b->h_fin_idx.grow(b->tot_fin_sel));
         if (n > 0) {
             HIP_TRY(hipMemcpyAsync(b->h_fin_off.p, b->fin.out_off.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, b->st));
             HIP_TRY(hipMemcpyAsync(b->h_fin_off.p + (n + 1), b->fin.sel_off.p, sizeof(uint64_t) * (n + 1),
                                    hipMemcpyDeviceToHost, b->st));
-            HIP_TRY(hipMemcpyAsync(b->h_fin_status.p, b->fin.status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, b->st));
         } else {
             b->h_fin_off.p[0] = b->h_fin_off.p[1] = 0;
         }
-        if (b->tot_fin) {
-            HIP_TRY(hipMemcpyAsync(b->h_fin_regs.p, b->fin.out_regs.p, sizeof(smem::AlnReg) * b->tot_fin,
-                                   hipMemcpyDeviceToHost, b->st));
-            HIP_TRY(hipMemcpyAsync(b->h_fin_sel.p, b->fin.out_sel.p, sizeof(smem::FinSel) * b->tot_fin,
-                                   hipMemcpyDeviceToHost, b->st));
-        }
-        if (b->tot_fin_sel)
-            HIP_TRY(hipMemcpyAsync(b->h_fin_idx.p, b->fin.out_idx.p, sizeof(uint64_t) * b->tot_fin_sel,
-                                   hipMemcpyDeviceToHost, b->st));
+        r = pull(b->h_fin_status, b->fin.status.p, (uint64_t)n);
+        if (!r) r = pull(b->h_fin_regs, b->fin.out_regs.p, b->tot_fin);
+        if (!r) r = pull(b->h_fin_sel, b->fin.out_sel.p, b->tot_fin);
+        if (!r) r = pull(b->h_fin_idx, b->fin.out_idx.p, b->tot_fin_sel);
     }
-    if (f_g2a) {
-        HIP_TRY(b->h_g2a_off.grow((uint64_t)n + 1));
-        HIP_TRY(b->h_g2a_alns.grow(b->tot_g2a));
-        HIP_TRY(b->h_g2a_rid.grow(b->tot_g2a));
-        HIP_TRY(b->h_g2a_cigar.grow(b->tot_g2a_cigar));
-        HIP_TRY(b->h_g2a_md.grow(b->tot_g2a_md));
-        if (n > 0)
-            HIP_TRY(hipMemcpyAsync(b->h_g2a_off.p, b->g2a_own_idx ? b->g2a.idx_off.p : b->fin.sel_off.p,
-                                   sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, b->st));
-        else
-            b->h_g2a_off.p[0] = 0;
-        if (b->tot_g2a) {
-            HIP_TRY(hipMemcpyAsync(b->h_g2a_alns.p, b->g2a.alns.p, sizeof(smem::Aln) * b->tot_g2a, hipMemcpyDeviceToHost,
-                                   b->st));
-            HIP_TRY(hipMemcpyAsync(b->h_g2a_rid.p, b->g2a.rid.p, sizeof(int32_t) * b->tot_g2a, hipMemcpyDeviceToHost,
-                                   b->st));
-        }
-        if (b->tot_g2a_cigar)
-            HIP_TRY(hipMemcpyAsync(b->h_g2a_cigar.p, b->g2a.cigar.p, sizeof(uint32_t) * b->tot_g2a_cigar,
-                                   hipMemcpyDeviceToHost, b->st));
-        if (b->tot_g2a_md)
-            HIP_TRY(hipMemcpyAsync(b->h_g2a_md.p, b->g2a.md.p, b->tot_g2a_md, hipMemcpyDeviceToHost, b->st));
-    }
-    if (f_sam) {
-        HIP_TRY(b->h_sam_off.grow((uint64_t)n + 1));
-        HIP_TRY(b->h_sam_status.grow((uint64_t)std::max(n, 1)));
-        HIP_TRY(b->h_sam_text.grow(b->tot_sam));
+    if (!r && f_g2a) {
         if (n > 0) {
-            HIP_TRY(hipMemcpyAsync(b->h_sam_off.p, b->sam.text_off.p, sizeof(uint64_t) * (n + 1), hipMemcpyDeviceToHost, b->st));
-            HIP_TRY(hipMemcpyAsync(b->h_sam_status.p, b->sam.status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, b->st));
+            r = pull(b->h_g2a_off, b->g2a_own_idx ? b->g2a.idx_off.p : b->fin.sel_off.p, (uint64_t)n + 1);
         } else {
+            HIP_TRY(b->h_g2a_off.grow(1));
+            b->h_g2a_off.p[0] = 0;
+        }
+        if (!r) r = pull(b->h_g2a_alns, b->g2a.alns.p, b->tot_g2a);
+        if (!r) r = pull(b->h_g2a_rid, b->g2a.rid.p, b->tot_g2a);
+        if (!r) r = pull(b->h_g2a_cigar, b->g2a.cigar.p, b->tot_g2a_cigar);
+        if (!r) r = pull(b->h_g2a_md, b->g2a.md.p, b->tot_g2a_md);
+    }
+    if (!r && f_sam) {
+        if (n > 0) {
+            r = pull(b->h_sam_off, b->sam.text_off.p, (uint64_t)n + 1);
+        } else {
+            HIP_TRY(b->h_sam_off.grow(1));
             b->h_sam_off.p[0] = 0;
         }
-        if (b->tot_sam)
-            HIP_TRY(hipMemcpyAsync(b->h_sam_text.p, b->sam.text.p, b->tot_sam, hipMemcpyDeviceToHost, b->st));
+        if (!r) r = pull(b->h_sam_status, b->sam.status.p, (uint64_t)n);
+        if (!r) r = pull(b->h_sam_text, b->sam.text.p, b->tot_sam);
     }
+    if (r) return r;
     INJECT(ST_FETCH);
     HIP_TRY(hipStreamSynchronize(b->st));
-    b->sam_fetched = f_sam;
-    b->fin_fetched = f_fin;
-    b->g2a_fetched = f_g2a;
-    b->fetched = f_intv;
-    b->sa_fetched = f_sa;
-    b->chain_fetched = f_chain;
-    b->aln_fetched = f_aln;
+    b->fetched = mask;
     return SMEM_OK;
 }
 
 int smem_batch_fetch(smem_batch_t* b) {
     g_err[0] = 0;
-    if (!b || !b->ran) return fail(SMEM_E_ARG, "smem_batch_fetch: batch has not run");
+    if (!b || b->stage < STAGE_SEEDED) return fail(SMEM_E_ARG, "smem_batch_fetch: batch has not run");
     return fetch_impl(b, SMEM_FETCH_ALL);
 }
 
 int smem_batch_fetch_mask(smem_batch_t* b, int mask) {
     g_err[0] = 0;
-    if (!b || !b->ran) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: batch has not run");
-    if (mask & ~(SMEM_FETCH_ALL | SMEM_FETCH_FIN | SMEM_FETCH_ALN | SMEM_FETCH_SAM)) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: unknown bits");
-    if (((mask & SMEM_FETCH_SA) && !b->sa_ran) || ((mask & SMEM_FETCH_CHAINS) && !b->chain_ran) ||
-        ((mask & SMEM_FETCH_REGS) && !b->aln_ran) || ((mask & SMEM_FETCH_FIN) && !b->fin_ran) ||
-        ((mask & SMEM_FETCH_ALN) && !b->g2a_ran) || ((mask & SMEM_FETCH_SAM) && !b->sam_ran))
+    if (!b || b->stage < STAGE_SEEDED) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: batch has not run");
+    if (mask & ~k_fetch_any) return fail(SMEM_E_ARG, "smem_batch_fetch_mask: unknown bits");
+    if (mask & ~stage_outputs(b))
         return fail(SMEM_E_ARG, "smem_batch_fetch_mask: a requested stage has not run on this batch");
     return fetch_impl(b, mask);
 }
@@ -1798,15 +1809,13 @@ static int load_sa_impl(smem_gpu_t* g, const smem_sa_t* sa) {
 
 int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
     g_err[0] = 0;
-    if (!b || !b->ran) return fail(SMEM_E_ARG, "smem_batch_sa: batch has not run");
+    if (!b || b->stage < STAGE_SEEDED) return fail(SMEM_E_ARG, "smem_batch_sa: batch has not run");
     smem_gpu_t* g = b->g;
     if (!g->d_sa) return fail(SMEM_E_ARG, "smem_batch_sa: no SA loaded (smem_gpu_load_sa)");
     if (max_occ < 0) return fail(SMEM_E_ARG, "smem_batch_sa: max_occ");
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->sa_ran = b->chain_ran = b->aln_ran = false;
-    b->sa_fetched = b->chain_fetched = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
+    stage_begin(b, STAGE_SA);
     // the densified SA may still be in the making (smem_gpu_load_sa runs it
     // in the background): until its event has passed, the walk goes to the
     // stored samples instead (the same positions, sa_intv / D times the LF
@@ -1823,8 +1832,8 @@ int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
             sa_shift = g->sa_shift_raw;
         } else if (q != hipSuccess) {
             return fail(SMEM_E_DEVICE, "smem_batch_sa: densification", q);
-        } else if (g->d_link) {
-            HIP_TRY(release_link(g, false));
+        } else {
+            HIP_TRY(release_link(g, false));  // (a no-op once the link scratch is gone)
         }
     }
     const uint64_t ni = b->tot_intv;
@@ -1868,12 +1877,8 @@ int smem_batch_sa(smem_batch_t* b, int min_seed_len, int max_occ) {
     HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
     b->stats.sa_ms = ms;
     b->stats.n_occ = b->tot_occ;
-    b->sa_ran = true;
-    b->sa_fetched = false;
     b->sa_min_seed_len = min_seed_len;
-    b->chain_ran = b->chain_fetched = false;
-    b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
+    stage_done(b, STAGE_SA);
     return SMEM_OK;
 }
 
@@ -1888,14 +1893,12 @@ void smem_chain_opt_default(smem_chain_opt_t* o) {
 
 int smem_batch_chain(smem_batch_t* b, int64_t l_pac, const smem_chain_opt_t* opt) {
     g_err[0] = 0;
-    if (!b || !b->sa_ran) return fail(SMEM_E_ARG, "smem_batch_chain: run smem_batch_sa first");
+    if (!b || b->stage < STAGE_SA) return fail(SMEM_E_ARG, "smem_batch_chain: run smem_batch_sa first");
     if (!opt || l_pac < 0 || opt->w < 0) return fail(SMEM_E_ARG, "smem_batch_chain: bad options");
     if (b->tot_occ >= (1ull << 32) - 1) return fail(SMEM_E_CAPACITY, "smem_batch_chain: too many seed occurrences");
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->chain_ran = b->aln_ran = false;
-    b->chain_fetched = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
+    stage_begin(b, STAGE_CHAINED);
     const int n = b->n_reads;
     const uint64_t no = std::max<uint64_t>(b->tot_occ, 1);
     HIP_TRY(b->d_seed.grow(no));
@@ -1999,17 +2002,14 @@ int smem_batch_chain(smem_batch_t* b, int64_t l_pac, const smem_chain_opt_t* opt
     HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
     b->stats.chain_ms = ms;
     b->stats.n_chains = b->tot_chains;
-    b->chain_ran = true;
-    b->chain_fetched = false;
     b->chain_filtered = opt->filter != 0;
-    b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
+    stage_done(b, STAGE_CHAINED);
     return SMEM_OK;
 }
 
 int smem_batch_chain_results(const smem_batch_t* b, const smem_chain_t** chains, const uint64_t** chain_off,
                              const smem_seed_t** seeds, uint64_t* n_chains, uint64_t* n_seeds) {
-    if (!b || !b->chain_fetched) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_CHAINS)) return SMEM_E_ARG;
     if (chains) *chains = reinterpret_cast<const smem_chain_t*>(b->h_out_chain.p);
     if (chain_off) *chain_off = b->h_chain_off.p;
     if (seeds) *seeds = reinterpret_cast<const smem_seed_t*>(b->h_out_seed.p);
@@ -2019,7 +2019,7 @@ int smem_batch_chain_results(const smem_batch_t* b, const smem_chain_t** chains,
 }
 
 int smem_batch_sa_results(const smem_batch_t* b, const uint64_t** pos, const uint64_t** occ_off, uint64_t* n_occ) {
-    if (!b || !b->sa_fetched) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_SA)) return SMEM_E_ARG;
     if (pos) *pos = b->h_sa_pos.p;
     if (occ_off) *occ_off = b->h_occ_off.p;
     if (n_occ) *n_occ = b->tot_occ;
@@ -2028,7 +2028,7 @@ int smem_batch_sa_results(const smem_batch_t* b, const uint64_t** pos, const uin
 
 int smem_batch_read(const smem_batch_t* b, int i, const smem_intv_t** intv, int* n_intv, const uint32_t** call_n,
                     int* n_calls) {
-    if (!b || !b->fetched || b->packed || i < 0 || i >= b->n_reads) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_INTV) || b->packed || i < 0 || i >= b->n_reads) return SMEM_E_ARG;
     const uint64_t o = b->h_intv_off.p[i], co = b->h_call_off.p[i];
     if (intv) *intv = reinterpret_cast<const smem_intv_t*>(b->h_intv.p + o);
     if (n_intv) *n_intv = (int)(b->h_intv_off.p[i + 1] - o);
@@ -2039,7 +2039,7 @@ int smem_batch_read(const smem_batch_t* b, int i, const smem_intv_t** intv, int*
 
 int smem_batch_results_packed(const smem_batch_t* b, const smem_pintv_t** pintv, const uint64_t** intv_off,
                               const uint32_t** call_n, const uint64_t** call_off) {
-    if (!b || !b->fetched || !b->packed) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_INTV) || !b->packed) return SMEM_E_ARG;
     if (pintv) *pintv = reinterpret_cast<const smem_pintv_t*>(b->h_pintv.p);
     if (intv_off) *intv_off = b->h_intv_off.p;
     if (call_n) *call_n = b->h_calls.p;
@@ -2049,7 +2049,7 @@ int smem_batch_results_packed(const smem_batch_t* b, const smem_pintv_t** pintv,
 
 int smem_batch_results(const smem_batch_t* b, const smem_intv_t** intv, const uint64_t** intv_off,
                        const uint32_t** call_n, const uint64_t** call_off) {
-    if (!b || !b->fetched || b->packed) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_INTV) || b->packed) return SMEM_E_ARG;
     if (intv) *intv = reinterpret_cast<const smem_intv_t*>(b->h_intv.p);
     if (intv_off) *intv_off = b->h_intv_off.p;
     if (call_n) *call_n = b->h_calls.p;
@@ -2098,21 +2098,11 @@ int smem_ksw_extend(smem_gpu_t* g, int n, const smem_ksw_task_t* tasks, const ui
     DevBuf<smem::KswTask> dt;
     DevBuf<smem::KswResult> dr;
     DevBuf<uint8_t> dq, dtg, dsc;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Guard {
-        DevBuf<smem::KswTask>& a; DevBuf<smem::KswResult>& b; DevBuf<uint8_t>& c; DevBuf<uint8_t>& d;
-        DevBuf<uint8_t>& f; hipEvent_t* e;
-        ~Guard() {
-            a.release(); b.release(); c.release(); d.release(); f.release();
-            if (e[0]) (void)hipEventDestroy(e[0]);
-            if (e[1]) (void)hipEventDestroy(e[1]);
-        }
-    } guard{dt, dr, dq, dtg, dsc, ev};
+    Events<2> ev;
     DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
     if (call.rc) return call.rc;
     const hipStream_t st = call.st;
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
+    HIP_TRY(ev.create());
     HIP_TRY(dt.ensure(n));
     HIP_TRY(dr.ensure(n));
     HIP_TRY(dq.ensure(q_bytes + 64));
@@ -2194,21 +2184,11 @@ int smem_ksw_align2(smem_gpu_t* g, int n, const smem_ksw_atask_t* tasks, const u
     DevBuf<smem::KswATask> dt;
     DevBuf<smem::KswAResult> dr;
     DevBuf<uint8_t> dq, dtg;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Guard {
-        DevBuf<smem::KswATask>& a; DevBuf<smem::KswAResult>& b; DevBuf<uint8_t>& c; DevBuf<uint8_t>& d;
-        hipEvent_t* e;
-        ~Guard() {
-            a.release(); b.release(); c.release(); d.release();
-            if (e[0]) (void)hipEventDestroy(e[0]);
-            if (e[1]) (void)hipEventDestroy(e[1]);
-        }
-    } guard{dt, dr, dq, dtg, ev};
+    Events<2> ev;
     DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
     if (call.rc) return call.rc;
     const hipStream_t st = call.st;
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
+    HIP_TRY(ev.create());
     HIP_TRY(dt.ensure(n));
     HIP_TRY(dr.ensure(n));
     HIP_TRY(dq.ensure(q_bytes + 64));
@@ -2692,7 +2672,7 @@ static int run_aln(smem_gpu_t* g, smem::AlnParams& P, uint64_t n_chains, uint64_
 
 int smem_batch_chain2aln(smem_batch_t* b, const smem_aln_opt_t* opt) {
     g_err[0] = 0;
-    if (!b || !b->chain_ran || !b->chain_filtered)
+    if (!b || b->stage < STAGE_CHAINED || !b->chain_filtered)
         return fail(SMEM_E_ARG, "smem_batch_chain2aln: run smem_batch_chain with filter = 1 first");
     if (!aln_opt_ok(opt)) return fail(SMEM_E_ARG, "smem_batch_chain2aln: scoring needs e >= 1, o >= 0, a >= 1, w >= 0");
     smem_gpu_t* g = b->g;
@@ -2700,8 +2680,7 @@ int smem_batch_chain2aln(smem_batch_t* b, const smem_aln_opt_t* opt) {
     if (b->max_len > 1024) return fail(SMEM_E_ARG, "smem_batch_chain2aln: reads longer than 1024 bp");
     BatchCall call(b, aln_two_streams());
     if (call.rc) return call.rc;
-    b->aln_ran = b->aln_fetched = false;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
+    stage_begin(b, STAGE_REGIONS);
     const int n = b->n_reads;
     const uint64_t ns = std::max<uint64_t>(b->tot_seeds, 1);
     HIP_TRY(b->d_aln_srt.grow(ns + 1));
@@ -2726,10 +2705,6 @@ int smem_batch_chain2aln(smem_batch_t* b, const smem_aln_opt_t* opt) {
     // bin-hash containment walks, chains over 64 seeds | their seeds << 32, bin-list hops)
     const char* cyc_path = getenv("SMEM_ALN_CYCLES");
     DevBuf<uint64_t> d_cyc;
-    struct Free {
-        DevBuf<uint64_t>& b;
-        ~Free() { b.release(); }  // every return path, HIP_TRY's included
-    } free_cyc{d_cyc};
     if (cyc_path) {
         HIP_TRY(d_cyc.ensure(5 * (uint64_t)std::max(n, 1)));
         HIP_TRY(hipMemsetAsync(d_cyc.p, 0, 5 * sizeof(uint64_t) * (uint64_t)std::max(n, 1), b->st));
@@ -2738,7 +2713,6 @@ int smem_batch_chain2aln(smem_batch_t* b, const smem_aln_opt_t* opt) {
     // SMEM_ALN_SPLIT=1: aln_kernel's cycles by phase and its counts (smem::Split), on stderr
     const bool split = getenv("SMEM_ALN_SPLIT") && atoi(getenv("SMEM_ALN_SPLIT"));
     DevBuf<uint64_t> d_split;
-    Free free_split{d_split};
     if (split) {
         HIP_TRY(d_split.ensure(smem::ALN_SPLITS));
         HIP_TRY(hipMemsetAsync(d_split.p, 0, smem::ALN_SPLITS * sizeof(uint64_t), b->st));
@@ -2789,14 +2763,13 @@ int smem_batch_chain2aln(smem_batch_t* b, const smem_aln_opt_t* opt) {
         for (int k = 0; k < smem::ALN_SPLITS; ++k) fprintf(stderr, " %llu", (unsigned long long)h[k]);
         fprintf(stderr, "\n");
     }
-    b->aln_ran = true;
-    b->aln_fetched = false;
+    stage_done(b, STAGE_REGIONS);
     return SMEM_OK;
 }
 
 int smem_batch_aln_results(const smem_batch_t* b, const smem_alnreg_t** regs, const uint64_t** reg_off,
                            uint64_t* n_regs) {
-    if (!b || !b->aln_fetched) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_REGS)) return SMEM_E_ARG;
     if (regs) *regs = reinterpret_cast<const smem_alnreg_t*>(b->h_aln_regs.p);
     if (reg_off) *reg_off = b->h_aln_regoff.p;
     if (n_regs) *n_regs = b->tot_regs;
@@ -2864,29 +2837,13 @@ int smem_chain2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint6
     DevBuf<uint32_t> dctr;
     AlnHeavyBufs heavy;
     HostBuf<uint64_t> hs, hnr;  // pinned: the scalars and region counts copied back
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Guard {
-        std::vector<std::function<void()>> f;
-        ~Guard() {
-            for (auto& x : f) x();
-        }
-    } guard;
-    guard.f.push_back([&] {
-        dcodes.release(); dpac.release(); doffs.release(); dchoff.release(); dseedoff.release(); dsrt.release();
-        dnregs.release(); dregoff.release(); dch.release(); dseeds.release(); draw.release(); dout.release();
-        dctr.release();
-        heavy.release();
-        hs.release(); hnr.release();
-        if (ev[0]) (void)hipEventDestroy(ev[0]);
-        if (ev[1]) (void)hipEventDestroy(ev[1]);
-    });
+    Events<2> ev;
     DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
     if (call.rc) return call.rc;
     const hipStream_t st = call.st;
     HIP_TRY(hs.ensure(8));
     HIP_TRY(hnr.ensure((size_t)n_reads));
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
+    HIP_TRY(ev.create());
     const uint64_t pac_bytes = (uint64_t)(l_pac + 3) / 4;
     HIP_TRY(dcodes.ensure(n_bases + 64));
     if (pac) HIP_TRY(dpac.ensure(pac_bytes + 64));
@@ -3067,20 +3024,11 @@ int smem_reg2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_
     DevBuf<char> dmd;
     DevBuf<unsigned long long> dcur;
     std::vector<uint64_t> off0;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct Guard {
-        std::function<void()> f;
-        ~Guard() { f(); }
-    } guard{[&] {
-        dcodes.release(); dpac.release(); dscratch.release(); dregs.release(); doffs.release(); dregoff.release();
-        dtask.release(); dlist.release(); dcig.release(); dcnt.release(); daln.release(); dmd.release(); dcur.release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }};
+    Events<5> ev;
     DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
     if (call.rc) return call.rc;
     const hipStream_t st = call.st;
-    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ev.create());
     const uint64_t pac_bytes = (uint64_t)(l_pac + 3) / 4;
     HIP_TRY(dcodes.ensure(n_bases + 64));
     if (pac) HIP_TRY(dpac.ensure(pac_bytes + 64));
@@ -3114,7 +3062,7 @@ int smem_reg2aln(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_
     R.PP.task = dtask.p, R.PP.list = dlist.p, R.PP.cnt = dcnt.p, R.PP.cur = dcur.p, R.PP.alns = daln.p;
     R.P.codes = dcodes.p, R.P.pac = pac ? dpac.p : g->d_pac;
     R.P.cigar = dcig.p, R.P.md = dmd.p, R.P.cigar_cap = cigar_cap, R.P.md_cap = md_cap;
-    R.h_cnt = h_cnt, R.h_cur = h_cur, R.scratch = &dscratch, R.ev = ev;
+    R.h_cnt = h_cnt, R.h_cur = h_cur, R.scratch = &dscratch, R.ev = ev.e;
     if (int rc = run_g2a(R, st)) return rc;
     if (kernel_ms) *kernel_ms = (double)R.ms_dp;
     if (h_cnt[smem::G2A_N_BADTRACE]) return fail(SMEM_E_INTERNAL, "smem_reg2aln: a region's traceback left its band");
@@ -3264,20 +3212,12 @@ int smem_reg_finalize(smem_gpu_t* g, int n_reads, const int* read_len, const sme
     FinBufs F;
     HostBuf<uint64_t> htot;
     std::vector<uint64_t> off0;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct Guard {
-        std::function<void()> f;
-        ~Guard() { f(); }
-    } guard{[&] {
-        dregs.release(); dregoff.release(); dlen.release(); dids.release(); F.release(); htot.release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }};
+    Events<5> ev;
     DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
     if (call.rc) return call.rc;
     const hipStream_t st = call.st;
     if (int rc = fin_tables(g)) return rc;
-    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ev.create());
     HIP_TRY(dregs.ensure(n_regs));
     HIP_TRY(dregoff.ensure((uint64_t)n_reads + 1));
     HIP_TRY(dlen.ensure((uint64_t)n_reads));
@@ -3298,7 +3238,7 @@ int smem_reg_finalize(smem_gpu_t* g, int n_reads, const int* read_len, const sme
     std::memset(&P, 0, sizeof(P));
     fin_params(P, g, F, opt, n_reads, n_regs, id0);
     P.regs = dregs.p, P.reg_off = dregoff.p, P.read_len = dlen.p, P.ids = ids ? dids.p : nullptr;
-    if (int rc = run_fin(P, F, ev, st)) return rc;
+    if (int rc = run_fin(P, F, ev.e, st)) return rc;
     HIP_TRY(hipMemcpyAsync(htot.p, F.out_off.p + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(htot.p + 1, F.sel_off.p + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     INJECT(ST_FIN);
@@ -3322,12 +3262,12 @@ int smem_reg_finalize(smem_gpu_t* g, int n_reads, const int* read_len, const sme
 
 int smem_batch_reg_finalize(smem_batch_t* b, const int64_t* ids, int64_t id0, const smem_fin_opt_t* opt) {
     g_err[0] = 0;
-    if (!b || !b->aln_ran) return fail(SMEM_E_ARG, "smem_batch_reg_finalize: run smem_batch_chain2aln first");
+    if (!b || b->stage < STAGE_REGIONS) return fail(SMEM_E_ARG, "smem_batch_reg_finalize: run smem_batch_chain2aln first");
     if (!fin_opt_ok(opt)) return fail(SMEM_E_ARG, "smem_batch_reg_finalize: options need a >= 1, b >= 0 and known flags");
     smem_gpu_t* g = b->g;
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->fin_ran = b->fin_fetched = b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
+    stage_begin(b, STAGE_FINAL);
     g->fin_used.store(true);  // slots reserved from now on carry the stage's buffers
     const int n = b->n_reads;
     if (int rc = fin_tables(g)) return rc;
@@ -3361,14 +3301,14 @@ int smem_batch_reg_finalize(smem_batch_t* b, const int64_t* ids, int64_t id0, co
         b->stats.fin_ms = ms, b->stats.fin_lane_ms = ms_lane, b->stats.fin_wave_ms = ms_wave;
     }
     b->stats.n_fin = b->tot_fin, b->stats.n_fin_sel = b->tot_fin_sel;
-    b->fin_ran = true;
+    stage_done(b, STAGE_FINAL);
     return SMEM_OK;
 }
 
 int smem_batch_fin_results(const smem_batch_t* b, const smem_alnreg_t** regs_out, const uint64_t** out_off,
                            const smem_fin_sel_t** sel, const uint64_t** sel_idx, const uint64_t** sel_off,
                            const int32_t** status, uint64_t* n_out, uint64_t* n_sel) {
-    if (!b || !b->fin_fetched) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_FIN)) return SMEM_E_ARG;
     if (regs_out) *regs_out = reinterpret_cast<const smem_alnreg_t*>(b->h_fin_regs.p);
     if (out_off) *out_off = b->h_fin_off.p;
     if (sel) *sel = reinterpret_cast<const smem_fin_sel_t*>(b->h_fin_sel.p);
@@ -3459,7 +3399,7 @@ static bool g2a_pool_estimate(uint64_t* words, uint64_t* bytes) {
 
 int smem_batch_reg2aln(smem_batch_t* b, const smem_aln_opt_t* opt, const uint64_t* idx, const uint64_t* idx_off) {
     g_err[0] = 0;
-    if (!b || !b->fin_ran) return fail(SMEM_E_ARG, "smem_batch_reg2aln: run smem_batch_reg_finalize first");
+    if (!b || b->stage < STAGE_FINAL) return fail(SMEM_E_ARG, "smem_batch_reg2aln: run smem_batch_reg_finalize first");
     if (!aln_opt_ok(opt)) return fail(SMEM_E_ARG, "smem_batch_reg2aln: scoring needs e >= 1, o >= 0, a >= 1, w >= 0");
     smem_gpu_t* g = b->g;
     if (!g->d_pac || g->l_pac <= 0) return fail(SMEM_E_ARG, "smem_batch_reg2aln: no resident .pac (smem_gpu_load_pac)");
@@ -3478,7 +3418,7 @@ int smem_batch_reg2aln(smem_batch_t* b, const smem_aln_opt_t* opt, const uint64_
     if (n_rec >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_batch_reg2aln: too many records");
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->g2a_ran = b->g2a_fetched = b->sam_ran = b->sam_fetched = false;
+    stage_begin(b, STAGE_ALIGNED);
     g->g2a_used.store(true);  // slots reserved from now on carry the stage's buffers
     G2aBufs& G = b->g2a;
     if (int rc = g2a_bufs_size(G, n_rec)) return rc;
@@ -3504,7 +3444,7 @@ int smem_batch_reg2aln(smem_batch_t* b, const smem_aln_opt_t* opt, const uint64_
     if (n_rec == 0) {
         INJECT(ST_G2A);
         HIP_TRY(hipStreamSynchronize(b->st));
-        b->g2a_ran = true;
+        stage_done(b, STAGE_ALIGNED);
         return SMEM_OK;
     }
     uint32_t* h_cnt = reinterpret_cast<uint32_t*>(b->h_g2a_ctr.p);
@@ -3540,14 +3480,14 @@ int smem_batch_reg2aln(smem_batch_t* b, const smem_aln_opt_t* opt, const uint64_
     }
     b->tot_g2a = n_rec, b->tot_g2a_cigar = h_cur[0], b->tot_g2a_md = h_cur[1];
     S.n_g2a = n_rec, S.n_g2a_deferred = h_cur[2], S.n_g2a_xref = h_cnt[smem::G2A_N_XREF];
-    b->g2a_ran = true;
+    stage_done(b, STAGE_ALIGNED);
     return SMEM_OK;
 }
 
 int smem_batch_aln2_results(const smem_batch_t* b, const smem_aln_t** alns, const int32_t** rid,
                             const uint64_t** aln_off, const uint32_t** cigar, uint64_t* n_cigar_words, const char** md,
                             uint64_t* n_md_bytes, uint64_t* n_alns) {
-    if (!b || !b->g2a_fetched) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_ALN)) return SMEM_E_ARG;
     if (alns) *alns = reinterpret_cast<const smem_aln_t*>(b->h_g2a_alns.p);
     if (rid) *rid = b->h_g2a_rid.p;
     if (aln_off) *aln_off = b->h_g2a_off.p;
@@ -3621,7 +3561,8 @@ int smem_batch_set_read_text(smem_batch_t* b, const char* names, const uint64_t*
     const uint64_t nc = comments ? comment_off[n] - comment_off[0] : 0;
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->text_set = b->sam_ran = b->sam_fetched = false;
+    stage_begin(b, STAGE_SAMTEXT);  // text printed from the old read text ends
+    b->text_set = false;
     SamBufs& S = b->sam;
     HIP_TRY(S.name_off.grow(N));
     HIP_TRY(S.names.grow(nn));
@@ -3717,7 +3658,7 @@ static int run_sam_write(SamPass& R, hipStream_t st) {
 
 int smem_batch_sam(smem_batch_t* b, const smem_sam_opt_t* opt) {
     g_err[0] = 0;
-    if (!b || !b->g2a_ran) return fail(SMEM_E_ARG, "smem_batch_sam: run smem_batch_reg2aln first");
+    if (!b || b->stage < STAGE_ALIGNED) return fail(SMEM_E_ARG, "smem_batch_sam: run smem_batch_reg2aln first");
     if (b->g2a_own_idx)
         return fail(SMEM_E_ARG, "smem_batch_sam: smem_batch_reg2aln ran over the caller's index lists (no MAPQ or flags per record)");
     smem_gpu_t* g = b->g;
@@ -3731,7 +3672,7 @@ int smem_batch_sam(smem_batch_t* b, const smem_sam_opt_t* opt) {
     if (rg_len > SAM_RG_MAX) return fail(SMEM_E_ARG, "smem_batch_sam: rg_id of more than 1023 bytes");
     BatchCall call(b);
     if (call.rc) return call.rc;
-    b->sam_ran = b->sam_fetched = false;
+    stage_begin(b, STAGE_SAMTEXT);
     g->sam_used.store(true);  // slots reserved from now on carry the stage's buffers
     const int n = b->n_reads;
     const uint64_t n_rec = b->tot_g2a;
@@ -3745,7 +3686,7 @@ int smem_batch_sam(smem_batch_t* b, const smem_sam_opt_t* opt) {
     if (n == 0) {
         INJECT(ST_SAM);
         HIP_TRY(hipStreamSynchronize(b->st));
-        b->sam_ran = true;
+        stage_done(b, STAGE_SAMTEXT);
         return SMEM_OK;
     }
     if (rg_len) {
@@ -3778,13 +3719,13 @@ int smem_batch_sam(smem_batch_t* b, const smem_sam_opt_t* opt) {
     b->tot_sam = total;
     T.sam_ms = (double)R.ms_len + (double)R.ms_write, T.sam_write_ms = (double)R.ms_write;
     T.n_sam_bytes = total, T.n_sam_host = cnt[smem::SAM_N_HOST];
-    b->sam_ran = true;
+    stage_done(b, STAGE_SAMTEXT);
     return SMEM_OK;
 }
 
 int smem_batch_sam_results(const smem_batch_t* b, const char** text, const uint64_t** text_off, const int32_t** status,
                            uint64_t* n_bytes) {
-    if (!b || !b->sam_fetched) return SMEM_E_ARG;
+    if (!b || !(b->fetched & SMEM_FETCH_SAM)) return SMEM_E_ARG;
     if (text) *text = b->h_sam_text.p;
     if (text_off) *text_off = b->h_sam_off.p;
     if (status) *status = b->h_sam_status.p;
@@ -3852,23 +3793,11 @@ int smem_sam_text(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64
     DevBuf<smem::SamRec> drec;
     DevBuf<uint32_t> dcig, dreclen, dsalen, dcnt;
     DevBuf<int64_t> dctg;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct Guard {
-        std::function<void()> f;
-        ~Guard() { f(); }
-    } guard{[&] {
-        dcodes.release(); dscan.release(); dqual.release(); dnames.release(); dcomm.release(); dmd.release();
-        dcn.release(); drg.release(); dtext.release(); doffs.release(); dnoff.release(); dcoff.release();
-        drecoff.release(); dcnoff.release(); dbytes.release(); dtoff.release(); daln.release(); drid.release();
-        dfst.release(); dstatus.release(); drec.release(); dcig.release(); dreclen.release(); dsalen.release();
-        dcnt.release(); dctg.release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }};
+    Events<4> ev;
     DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
     if (call.rc) return call.rc;
     const hipStream_t st = call.st;
-    for (hipEvent_t& e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ev.create());
     const uint64_t NR = std::max<uint64_t>(n_rec, 1);
     HIP_TRY(dcodes.ensure(n_bases));
     HIP_TRY(doffs.ensure(N));
@@ -3936,7 +3865,7 @@ int smem_sam_text(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64
     P.rg = drg.p, P.rg_len = (uint32_t)rg_len;
     P.rec_len = dreclen.p, P.sa_len = dsalen.p, P.read_bytes = dbytes.p, P.status = dstatus.p;
     P.text_off = dtoff.p, P.cnt = dcnt.p, P.text = dtext.p;
-    R.read_bytes = dbytes.p, R.text_off = dtoff.p, R.scan_tmp = &dscan, R.h_ctr = h_ctr, R.ev = ev, R.inject = ST_SAM;
+    R.read_bytes = dbytes.p, R.text_off = dtoff.p, R.scan_tmp = &dscan, R.h_ctr = h_ctr, R.ev = ev.e, R.inject = ST_SAM;
     if (int rc = run_sam_len(R, st)) return rc;
     if (kernel_ms) *kernel_ms = (double)R.ms_len;
     *n_bytes = h_ctr[0];
@@ -4335,7 +4264,7 @@ static int batch_warmup(smem_batch_t* b) {
     if (!rc && g->d_sa) rc = smem_batch_sa(b, so.min_seed_len, 10000);
     if (!rc && g->d_sa) rc = smem_batch_chain(b, g->l_pac, &co);
     if (!rc && g->d_sa && b->max_len <= 1024) rc = smem_batch_chain2aln(b, &ao);
-    if (!rc && b->aln_ran) rc = smem_batch_fetch_mask(b, SMEM_FETCH_REGS);
+    if (!rc && b->stage >= STAGE_REGIONS) rc = smem_batch_fetch_mask(b, SMEM_FETCH_REGS);
     return rc;
 }
 
