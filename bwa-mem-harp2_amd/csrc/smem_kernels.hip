@@ -345,6 +345,25 @@ __device__ __forceinline__ uint32_t idle_u32() {
     return v;
 }
 
+// A lane flag the compiler cannot trace back to the compares it came from (a v_cndmask and a v_cmp).
+// seed_wp_kernel SKIP: with fwdreq left as three compares of `phase`, every select by it below
+// (ra / rb / rs, the probe's sides) compiled to a branch tree over the phase's ranges, walked whole
+// by every wave-iteration (DESIGN.md §5 "The skipping arm's fixed cost")
+__device__ __forceinline__ bool lane_flag(bool b) {
+    uint32_t v = b ? 1u : 0u;
+    asm volatile("" : "+v"(v));
+    return v != 0u;
+}
+
+// seed_wp_kernel SKIP: the k-mer table's slot of a string of lq bases, its codes the low bits of `codes`
+// (top: the highest of K bases' worth).  Level lq starts at (4^lq - 4) / 3 = 0b0101..01 (lq ones) - 1;
+// lq is clipped to the table's levels (only a broken state is: the probe stays in the table)
+__device__ __forceinline__ uint32_t kt_slot(uint32_t codes, int lq, int K, bool top) {
+    lq = lq < 1 ? 1 : (lq > K ? K : lq);
+    const uint32_t code = (top ? codes >> (2 * (K - lq)) : codes) & ((1u << (2 * lq)) - 1u);
+    return (0x55555555u >> (32 - 2 * lq)) - 1u + code;
+}
+
 // LDS accesses of one wave execute in order; this keeps the compiler from
 // moving them across the point where another lane's write must be seen
 __device__ __forceinline__ void wave_lds_fence() {
@@ -449,7 +468,7 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
     uint32_t mem_last_start = ~0u;  // the start of the call's last record (~0: none yet, mem->n == 0)
     uint32_t max_len = 0, max_x2 = 0, max_mid = 0;
     uint4 head = {0, 0, 0, 0};  // prev[0] of the current step
-    uint64_t na = 0, nb = 0, ns = 0;
+    uint64_t na = 0, nb = 0, ns = 0;  // an extend's result (SKIP: before its own probe, an owner's na holds the table slot)
     if (P.tspan && me == 0) atomicMax(reinterpret_cast<unsigned long long*>(P.tspan), ~(unsigned long long)rtstamp());
 
 #define QBLK(pos) ((o0 + (uint32_t)(pos)) & ~15u)
@@ -734,7 +753,8 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
                     if (done) {
                         if (i - x >= 2) {
                             if (i < len) qwant = QBLK(i);
-                            phase = P_KRES;  // -> the probe of q[x, i), on this lane
+                            phase = P_KRES;  // -> the probe of q[x, i), on this lane (its slot waits in na)
+                            na = kt_slot(kc, i - x, K, false);
                             WP_OUT();
                         } else {
                             phase = P_FWD;
@@ -839,8 +859,12 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
                         // nothing extends: prev[0] is the only candidate (software/bwt.c:816-819)
                         phase = P_SMEM_END;
                         if ((uint32_t)(i + 1) < mem_last_start) {
-                            if (SKIP && prev_n == 0 && nv != 0) phase = P_KEND;  // prev[0] is virtual: -> its probe, on this lane
-                            else WP_EMIT(head);
+                            if (SKIP && prev_n == 0 && nv != 0) {  // prev[0] is virtual: -> its probe, on this lane
+                                phase = P_KEND;
+                                na = kt_slot(kc, (int)nv + x - i - 1, K, true);
+                            } else {
+                                WP_EMIT(head);
+                            }
                         }
                     }
                 }
@@ -850,8 +874,11 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
         if (!__any(phase != P_EXIT)) break;
         // (a lane is at P_FWD_RES here only when P_FWD has just set it: the P_FWD_RES block always leaves it)
         // (the same holds for SKIP's own probes, P_KRES / P_KEND: a lane that extends or probes for itself)
-        const bool ownp = SKIP && (phase == P_KRES || phase == P_KEND);
-        const bool fwdreq = ((DIET & 32) || out) && (phase == P_FWD_RES || ownp);
+        // (SKIP: both told from the phase once, by a bit test, and kept as lane flags, see lane_flag)
+        constexpr uint32_t OWNP_SET = 1u << P_KRES | 1u << P_KEND, FWD_SET = OWNP_SET | 1u << P_FWD_RES;
+        const bool ownp = SKIP && lane_flag(((1u << phase) & OWNP_SET) != 0u);
+        const bool fwdreq = SKIP ? lane_flag(((DIET & 32) || out) && ((1u << phase) & FWD_SET) != 0u)
+                                 : ((DIET & 32) || out) && phase == P_FWD_RES;
         const uint32_t rem = phase == P_BWD_WAIT ? prev_n + (SKIP ? fail0 >> 1 : 0u) - j : 0u;
         const uint32_t slots = (rem + PR - 1) / PR;  // worker lanes the step still needs
         if (!DPOS && rem) {  // what a worker needs of this owner's step
@@ -896,7 +923,9 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
         //    (surv, keep, rank == s, tabP[s], RES[pp], the stores into the owner's list) or under `far`,
         //    which only a worker sets -- obp, formed from `o` outside the branch, is dereferenced only
         //    there; a forward lane (fwdreq) takes ra / rb / rs / rc from its own state, never from ent / w0,
-        //    and the KT path reads w1.w only where !fwdreq, i.e. on a worker;
+        //    and the KT path reads w1.w only where !fwdreq, i.e. on a worker (SKIP: a lane that probes for
+        //    itself forms a slot from its arbitrary w1 as well and drops it for the one its own block left in
+        //    na; kt_slot clips either into the table);
         //  * k0, k1, l0, l1 are loaded under `task` and read under `task` (l0 / l1 only where bl != bk);
         //  * what comes out of arbitrary inputs in a lane without a task (kk, ll, bk, bl) reaches no
         //    address: every load and store below is under `task`, `far`, `keep` or `take`.
@@ -983,16 +1012,10 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
         uint4 k0 = WP_IDLE128(), k1 = WP_IDLE128(), l0 = WP_IDLE128(), l1 = WP_IDLE128();
         // KT: a result of at most K bases from the table (forward: q[x, i]; backward: q[i, end))
         bool ktp = false;
-        if constexpr (SKIP) {  // the only probes: an owner's own (start / end of a call), a step's last task
-            if (ownp || isp) {
-                int lq = ownp ? (phase == P_KRES ? i - x : (int)nv + x - i - 1) : (int)(w1.z >> 24);
-                lq = lq < 1 ? 1 : (lq > K ? K : lq);  // (only a broken state is clipped: the probe stays in the table)
-                const uint32_t code = (ownp ? (phase == P_KRES ? kc : kc >> (2 * (K - lq))) : w1.w >> (2 * (K - lq))) &
-                                      ((1u << (2 * lq)) - 1u);
-                // level lq starts at (4^lq - 4) / 3 = 0b0101..01 (lq ones) - 1
-                k0 = P.kt[(0x55555555u >> (32 - 2 * lq)) - 1u + code];
-                ktp = true;
-            }
+        if constexpr (SKIP) {  // the only probes: an owner's own (start / end of a call; the owner's block left
+            // the slot in na), a step's last task (the dp bases from position i, of the descriptor's K)
+            ktp = lane_flag(ownp || isp);
+            if (ktp) k0 = P.kt[ownp ? (uint32_t)na : kt_slot(w1.w, (int)(w1.z >> 24), K, true)];
         } else if constexpr (KT) {
             if (task && K > 0) {
                 const int lq = fwdreq ? i + 1 - x : (int)p_end(ent) - (int)(w0.w >> 10);
