@@ -179,6 +179,8 @@ struct KswAParams {
 
 extern "C" {
 hipError_t smem_launch_ksw_align2(const smem::KswAParams* K, int n_cu, hipStream_t st);
+// targets of up to smem::KSWA_MAX_TLEN rows (ksw_kernels.hip)
+hipError_t smem_launch_ksw_align2_long(const smem::KswAParams* K, int n_cu, hipStream_t st);
 // long_reads != 0: the batch holds reads of 257..1024 bp (second instantiation)
 hipError_t smem_launch_aln(const smem::AlnParams* P, int n_cu, int long_reads, hipStream_t st);
 hipError_t smem_launch_aln_write(const smem::AlnParams* P, hipStream_t st);

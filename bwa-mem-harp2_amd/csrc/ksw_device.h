@@ -415,10 +415,19 @@ struct SwOut {
 // column q - 1, which is the own block inside a block and the one before at
 // its first column, so one expression (fk) gives both; the choice between it
 // and the full prefix maximum is the same for the whole wave.
-template <class QF, class TF>
+//
+// LONG (tlen <= KSWA_MAX_TLEN): everything tied to tlen leaves the registers.
+// The target is fetched 64 rows at a time, one row per lane, as extend_wave
+// does; the list b, which merges consecutive rows and so holds at most
+// ceil(tlen / 2) entries, is the wave's own blist[2 KSWA_B_MAX] in LDS (the
+// scores, then the rows), written by lane 0; the selection after the loop
+// is a per-lane strict > scan over the entries lane, lane + 64, ... and a
+// wave reduction that takes the smallest index among the largest scores,
+// which is the entry the reference's strict > scan keeps.
+template <bool LONG = false, class QF, class TF>
 __device__ __forceinline__ SwOut sw_pass_wave(int p, int qlen, QF qsym, int tlen, TF tsym, const int8_t* mat,
                                               int o_del, int e_del, int o_ins, int e_ins, int minsc, int endsc,
-                                              int shift, int top) {
+                                              int shift, int top, int* blist = nullptr) {
     const int lane = threadIdx.x & 63;
     const bool u8 = p == 16;
     const int slen = (qlen + p - 1) / p, qp = slen * p;
@@ -440,17 +449,24 @@ __device__ __forceinline__ SwOut sw_pass_wave(int p, int qlen, QF qsym, int tlen
         }
         hp[c] = ee[c] = hm[c] = 0;
         sg[c] = q < qp ? q / slen : 0;
-        tv[c] = q < tlen ? (int)tsym(q) : 0;  // target row 64 c + lane
+        tv[c] = !LONG && q < tlen ? (int)tsym(q) : 0;  // target row 64 c + lane
     }
     int gmax = 0, te = -1;
     int bv[4] = {-1, -1, -1, -1}, br[4] = {0, 0, 0, 0};
     int n_b = 0, last_row = -2, last_val = 0;
+    int tcache = 0;
     for (int i = 0; i < tlen; ++i) {
-        const int ci = i >> 6;
-        int t = tv[0];
-        if (ci == 1) t = tv[1];
-        if (ci == 2) t = tv[2];
-        if (ci == 3) t = tv[3];
+        int t;
+        if constexpr (LONG) {
+            if ((i & 63) == 0) tcache = i + lane < tlen ? (int)tsym(i + lane) : 0;
+            t = tcache;
+        } else {
+            const int ci = i >> 6;
+            t = tv[0];
+            if (ci == 1) t = tv[1];
+            if (ci == 2) t = tv[2];
+            if (ci == 3) t = tv[3];
+        }
         t = rl(t, i & 63);
         int hn[4];
         int prev_last = 0, carry_b = NEG, carry_a = NEG, rmax = 0;
@@ -493,7 +509,9 @@ __device__ __forceinline__ SwOut sw_pass_wave(int p, int qlen, QF qsym, int tlen
             else if (last_val < rmax) idx = n_b - 1;
             if (idx >= 0) {
                 last_row = i, last_val = rmax;
-                if (lane == (idx & 63)) {
+                if constexpr (LONG) {
+                    if (lane == 0 && idx < KSWA_B_MAX) blist[idx] = rmax, blist[KSWA_B_MAX + idx] = i;
+                } else if (lane == (idx & 63)) {
                     const int slot = idx >> 6;
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
@@ -528,12 +546,33 @@ __device__ __forceinline__ SwOut sw_pass_wave(int p, int qlen, QF qsym, int tlen
         if (n_b) {
             const int d = (r.score + top - 1) / top, low = te - d, high = te + d;
             int cand = -1;
+            if constexpr (LONG) {
+                // lane 0's stores, then every lane's loads: same wave, LDS in order
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const int nb = imin(n_b, KSWA_B_MAX);
+                int ci = 0x7fffffff;  // this lane's first entry holding cand
+                for (int k0 = 0; k0 < nb; k0 += 64) {  // (a wave-uniform bound)
+                    const int k = k0 + lane;
+                    if (k < nb) {
+                        const int v = blist[k], row = blist[KSWA_B_MAX + k];
+                        if ((row < low || row > high) && v > cand) cand = v, ci = k;
+                    }
+                }
+                r.score2 = imax(-1, wave_max(cand));
+                if (r.score2 >= 0) {
+                    const int first = -wave_max(cand == r.score2 ? -ci : NEG);
+                    r.te2 = blist[KSWA_B_MAX + first];
+                }
+            } else {
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (64 * c + lane < n_b && (br[c] < low || br[c] > high)) cand = imax(cand, bv[c]);
-            r.score2 = imax(-1, wave_max(cand));
+                for (int c = 0; c < 4; ++c)
+                    if (64 * c + lane < n_b && (br[c] < low || br[c] > high)) cand = imax(cand, bv[c]);
+                r.score2 = imax(-1, wave_max(cand));
+            }
             // te2: the row of the first list entry holding score2 (the strict > scan)
-            if (r.score2 >= 0) {
+            if (!LONG && r.score2 >= 0) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const uint64_t hit = __ballot(64 * c + lane < n_b && (br[c] < low || br[c] > high) &&
@@ -554,19 +593,21 @@ struct SwAlign {
 // the pass over the reversed query [0, qe] and target (first te + 1 rows
 // reversed, the rest as is) that stops at the forward score; tb / qb = -1
 // unless that pass reaches the same score
-template <class QF, class TF>
+template <bool LONG = false, class QF, class TF>
 __device__ __forceinline__ SwAlign sw_align_wave(int qlen, QF qsym, int tlen, TF tsym, const int8_t* mat, int o_del,
-                                                 int e_del, int o_ins, int e_ins, int xtra, int shift, int top) {
+                                                 int e_del, int o_ins, int e_ins, int xtra, int shift, int top,
+                                                 int* blist = nullptr) {
     const int p = (xtra & SW_XBYTE) ? 16 : 8;
     const int minsc = (xtra & SW_XSUBO) ? xtra & 0xffff : 0x10000;
     const int endsc = (xtra & SW_XSTOP) ? xtra & 0xffff : 0x10000;
-    const SwOut r = sw_pass_wave(p, qlen, qsym, tlen, tsym, mat, o_del, e_del, o_ins, e_ins, minsc, endsc, shift, top);
+    const SwOut r =
+        sw_pass_wave<LONG>(p, qlen, qsym, tlen, tsym, mat, o_del, e_del, o_ins, e_ins, minsc, endsc, shift, top, blist);
     SwAlign a{r.score, r.te, r.qe, r.score2, r.te2, -1, -1};
     if ((xtra & SW_XSTART) == 0 || ((xtra & SW_XSUBO) && r.score < (xtra & 0xffff)) || r.qe < 0) return a;
     const int qe = r.qe, te = r.te;
-    const SwOut rr = sw_pass_wave(
+    const SwOut rr = sw_pass_wave<LONG>(
         p, qe + 1, [&](int q) { return qsym(qe - q); }, tlen, [&](int i) { return i <= te ? tsym(te - i) : tsym(i); },
-        mat, o_del, e_del, o_ins, e_ins, 0x10000, r.score, shift, top);
+        mat, o_del, e_del, o_ins, e_ins, 0x10000, r.score, shift, top, blist);
     if (r.score == rr.score) a.tb = te - rr.te, a.qb = qe - rr.qe;
     return a;
 }

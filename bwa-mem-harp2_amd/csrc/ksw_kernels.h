@@ -8,6 +8,13 @@ namespace smem {
 
 constexpr int KSW_COLS_PER_LANE = 4;  // query columns 0..qlen held per wave: qlen <= 255
 
+// ksw_align2 with long targets (smem_ksw_align2_long, the SWs of mem_matesw):
+// the longest target, and the entries its suboptimal list can hold -- rows
+// that follow each other share an entry, so ceil(tlen / 2) -- kept per wave
+// in LDS as 2 KSWA_B_MAX ints (scores, then rows): 8200 B a wave
+constexpr int KSWA_MAX_TLEN = 2048;  // SMEM_KSWA_MAX_TLEN
+constexpr int KSWA_B_MAX = KSWA_MAX_TLEN / 2 + 1;
+
 // smem_ksw_task_t / smem_ksw_result_t (include/smem_gpu.h)
 struct KswTask {
     uint64_t q_off, t_off;

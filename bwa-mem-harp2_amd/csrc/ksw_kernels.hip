@@ -21,6 +21,7 @@
 
 #include <algorithm>
 
+#include "aln_kernels.h"
 #include "ksw_kernels.h"
 #include "ksw_device.h"
 #include "ksw_lane.h"
@@ -261,6 +262,43 @@ extern "C" hipError_t smem_launch_ksw(const smem::KswParams* K, int n_cu, hipStr
     }
     const int waves = K->n < n_cu * 32 ? K->n : n_cu * 32;
     hipLaunchKernelGGL(smem::ksw_extend_kernel, dim3((waves + 3) / 4), dim3(256), 0, st, *K);
+    return hipGetLastError();
+}
+
+namespace smem {
+
+// ksw_align2 (software/ksw.c:342-364) of a batch of independent problems with
+// targets of up to KSWA_MAX_TLEN rows, one wave each (qlen <= 256): the query
+// columns in registers as in the short kernel (aln_kernels.hip), the target
+// fetched 64 rows at a time and the suboptimal list in the wave's own LDS
+// (kswd::sw_pass_wave<true>).  No block-wide barrier: the four waves of a block
+// share nothing.
+__global__ __launch_bounds__(256) void ksw_align2_long_kernel(KswAParams K) {
+    __shared__ int blist[4][2 * KSWA_B_MAX];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int n_waves = (int)((gridDim.x * blockDim.x) >> 6);
+    int* bl = blist[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
+    for (int it = wave; it < K.n; it += n_waves) {
+        const KswATask T = K.task[it];
+        const uint8_t* q = K.q + T.q_off;
+        const uint8_t* tg = K.t + T.t_off;
+        const int qlen = __builtin_amdgcn_readfirstlane(T.qlen), tlen = __builtin_amdgcn_readfirstlane(T.tlen);
+        const int xtra = __builtin_amdgcn_readfirstlane(T.xtra);
+        const kswd::SwAlign a = kswd::sw_align_wave<true>(
+            qlen, [&](int j) { return (int)q[j]; }, tlen, [&](int i) { return (int)tg[i]; }, K.mat, K.o_del, K.e_del,
+            K.o_ins, K.e_ins, xtra, K.shift, K.top, bl);
+        if (lane == 0) K.out[it] = KswAResult{a.score, a.te, a.qe, a.score2, a.te2, a.tb, a.qb};
+    }
+}
+
+}  // namespace smem
+
+extern "C" hipError_t smem_launch_ksw_align2_long(const smem::KswAParams* K, int n_cu, hipStream_t st) {
+    if (K->n <= 0) return hipSuccess;
+    // 32.8 KB of LDS a block: four blocks, 16 waves, a CU
+    const int waves = K->n < n_cu * 16 ? K->n : n_cu * 16;
+    hipLaunchKernelGGL(smem::ksw_align2_long_kernel, dim3((waves + 3) / 4), dim3(256), 0, st, *K);
     return hipGetLastError();
 }
 

@@ -40,6 +40,7 @@
 #include "global_kernels.h"
 #include "fin_kernels.h"
 #include "sam_kernels.h"
+#include "matesw_kernels.h"
 
 using smem::Intv;
 
@@ -97,13 +98,14 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
 // the drain on the way out is what keeps that work from landing after the
 // caller resumed.  stage: upload (smem_batch_set_reads*), seed
 // (smem_batch_run), sa, chain, aln (smem_batch_chain2aln), fin (smem_reg_finalize,
-// smem_batch_reg_finalize), g2a (smem_batch_reg2aln), sam (smem_batch_sam, smem_sam_text), fetch, or any.
+// smem_batch_reg_finalize), g2a (smem_batch_reg2aln), sam (smem_batch_sam, smem_sam_text), matesw (smem_matesw),
+// fetch, or any.
 // ":sticky" also marks the device faulted, as a real runtime failure does;
 // ":hip=<code>" goes through fail() with that hipError_t, so the
 // classification decides (hip=9, hipErrorInvalidConfiguration: that call only;
 // hip=719, hipErrorLaunchFailure: the device).
-enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_G2A, ST_SAM, ST_N };
-const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin", "g2a", "sam"};
+enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_G2A, ST_SAM, ST_MSW, ST_N };
+const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin", "g2a", "sam", "matesw"};
 std::atomic<uint64_t> g_stage_calls[ST_N];
 
 int inject_fault(int stage) {
@@ -2163,22 +2165,31 @@ int smem_ksw_extend(smem_gpu_t* g, int n, const smem_ksw_task_t* tasks, const ui
 static_assert(sizeof(smem_ksw_atask_t) == sizeof(smem::KswATask), "align task layout");
 static_assert(sizeof(smem_ksw_aresult_t) == sizeof(smem::KswAResult), "align result layout");
 
-int smem_ksw_align2(smem_gpu_t* g, int n, const smem_ksw_atask_t* tasks, const uint8_t* q, uint64_t q_bytes,
-                    const uint8_t* t, uint64_t t_bytes, const smem_ksw_opt_t* opt, smem_ksw_aresult_t* out,
-                    double* kernel_ms) {
+static_assert(SMEM_KSWA_MAX_TLEN == smem::KSWA_MAX_TLEN, "long-target limit");
+
+// smem_ksw_align2 (max_tlen 256: the register-resident kernel) and smem_ksw_align2_long
+// (SMEM_KSWA_MAX_TLEN: the kernel that keeps the target and the suboptimal list out of registers)
+static int ksw_align2_impl(smem_gpu_t* g, int n, const smem_ksw_atask_t* tasks, const uint8_t* q, uint64_t q_bytes,
+                           const uint8_t* t, uint64_t t_bytes, const smem_ksw_opt_t* opt, smem_ksw_aresult_t* out,
+                           double* kernel_ms, int max_tlen) {
+    const bool lng = max_tlen > 256;
     g_err[0] = 0;
-    if (!g || n < 0 || !opt || (n > 0 && (!tasks || !out))) return fail(SMEM_E_ARG, "smem_ksw_align2: bad arguments");
+    if (!g || n < 0 || !opt || (n > 0 && (!tasks || !out)))
+        return fail(SMEM_E_ARG, lng ? "smem_ksw_align2_long: bad arguments" : "smem_ksw_align2: bad arguments");
     if (opt->e_del < 1 || opt->e_ins < 1 || opt->o_del < 0 || opt->o_ins < 0)
-        return fail(SMEM_E_ARG, "smem_ksw_align2: gap penalties need e >= 1, o >= 0");
+        return fail(SMEM_E_ARG, lng ? "smem_ksw_align2_long: gap penalties need e >= 1, o >= 0"
+                                    : "smem_ksw_align2: gap penalties need e >= 1, o >= 0");
     for (int i = 0; i < n; ++i) {
         const smem_ksw_atask_t& k = tasks[i];
-        if (k.qlen < 1 || k.qlen > 256 || k.tlen < 0 || k.tlen > 256 || k.q_off + (uint64_t)k.qlen > q_bytes ||
+        if (k.qlen < 1 || k.qlen > 256 || k.tlen < 0 || k.tlen > max_tlen || k.q_off + (uint64_t)k.qlen > q_bytes ||
             k.t_off + (uint64_t)k.tlen > t_bytes)
-            return fail(SMEM_E_ARG, "smem_ksw_align2: task outside 1 <= qlen <= 256, tlen <= 256 or its pools");
+            return fail(SMEM_E_ARG,
+                        lng ? "smem_ksw_align2_long: task outside 1 <= qlen <= 256, tlen <= SMEM_KSWA_MAX_TLEN or its pools"
+                            : "smem_ksw_align2: task outside 1 <= qlen <= 256, tlen <= 256 or its pools");
     }
     // (a byte score that reaches the ceiling is returned as 255 with qe = -1, as ksw_u8 does: tests' kswa_sat sets)
     for (uint64_t k = 0; k < q_bytes; ++k)
-        if (q[k] > 4) return fail(SMEM_E_ARG, "smem_ksw_align2: query code > 4");
+        if (q[k] > 4) return fail(SMEM_E_ARG, lng ? "smem_ksw_align2_long: query code > 4" : "smem_ksw_align2: query code > 4");
     if (kernel_ms) *kernel_ms = 0.0;
     if (n == 0) return SMEM_OK;
     DevBuf<smem::KswATask> dt;
@@ -2210,7 +2221,8 @@ int smem_ksw_align2(smem_gpu_t* g, int n, const smem_ksw_atask_t* tasks, const u
         K.top = md, K.shift = (uint8_t)(256 - sh);
     }
     HIP_TRY(hipEventRecord(ev[0], st));
-    HIP_TRY(smem_launch_ksw_align2(&K, g->n_cu, st));
+    if (lng) HIP_TRY(smem_launch_ksw_align2_long(&K, g->n_cu, st));
+    else HIP_TRY(smem_launch_ksw_align2(&K, g->n_cu, st));
     HIP_TRY(hipEventRecord(ev[1], st));
     HIP_TRY(hipMemcpyAsync(out, dr.p, sizeof(smem::KswAResult) * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2218,6 +2230,18 @@ int smem_ksw_align2(smem_gpu_t* g, int n, const smem_ksw_atask_t* tasks, const u
     HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     if (kernel_ms) *kernel_ms = ms;
     return SMEM_OK;
+}
+
+int smem_ksw_align2(smem_gpu_t* g, int n, const smem_ksw_atask_t* tasks, const uint8_t* q, uint64_t q_bytes,
+                    const uint8_t* t, uint64_t t_bytes, const smem_ksw_opt_t* opt, smem_ksw_aresult_t* out,
+                    double* kernel_ms) {
+    return ksw_align2_impl(g, n, tasks, q, q_bytes, t, t_bytes, opt, out, kernel_ms, 256);
+}
+
+int smem_ksw_align2_long(smem_gpu_t* g, int n, const smem_ksw_atask_t* tasks, const uint8_t* q, uint64_t q_bytes,
+                         const uint8_t* t, uint64_t t_bytes, const smem_ksw_opt_t* opt, smem_ksw_aresult_t* out,
+                         double* kernel_ms) {
+    return ksw_align2_impl(g, n, tasks, q, q_bytes, t, t_bytes, opt, out, kernel_ms, SMEM_KSWA_MAX_TLEN);
 }
 
 void smem_aln_opt_default(smem_aln_opt_t* o) {
@@ -3257,6 +3281,156 @@ int smem_reg_finalize(smem_gpu_t* g, int n_reads, const int* read_len, const sme
     }
     if (n_sel) HIP_TRY(hipMemcpyAsync(sel_idx, F.out_idx.p, sizeof(uint64_t) * n_sel, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return SMEM_OK;
+}
+
+// ---- mate rescue (mem_matesw for the good hits of both ends: csrc/matesw_kernels.hip)
+static_assert(SMEM_MSW_HOST == smem::MSW_HOST, "mate rescue status");
+
+void smem_matesw_opt_default(smem_matesw_opt_t* o) {  // mem_opt_init (software/bwamem.c:48-75)
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    smem_ksw_opt_default(&o->sc);
+    o->a = 1, o->min_seed_len = 19, o->pen_unpaired = 17, o->max_matesw = 100, o->mask_level_redun = 0.95f;
+}
+
+int smem_matesw(smem_gpu_t* g, int n_pairs, const uint8_t* codes, const uint64_t* offs, const smem_alnreg_t* regs,
+                const uint64_t* reg_off, const smem_pestat_t pes[4], const uint8_t* pac, int64_t l_pac,
+                const smem_matesw_opt_t* opt, smem_alnreg_t* regs_out, uint64_t regs_cap, uint64_t* reg_off_out,
+                int32_t* n_sw, int32_t* status, uint64_t* n_regs_out, double* kernel_ms) {
+    g_err[0] = 0;
+    if (!g || n_pairs < 0 || n_pairs > (1 << 29) || !opt || !pes || !reg_off_out || !n_regs_out || l_pac <= 0 ||
+        (n_pairs > 0 && (!codes || !offs || !reg_off || !n_sw || !status)) || (regs_cap > 0 && !regs_out))
+        return fail(SMEM_E_ARG, "smem_matesw: bad arguments");
+    if (!pac && !(g->d_pac && g->l_pac == l_pac))
+        return fail(SMEM_E_ARG, "smem_matesw: no pac given and none resident for this l_pac (smem_gpu_load_pac)");
+    if (opt->sc.e_del < 1 || opt->sc.e_ins < 1 || opt->sc.o_del < 0 || opt->sc.o_ins < 0 || opt->a < 1 ||
+        opt->min_seed_len < 0 || (int64_t)opt->min_seed_len * opt->a > 0xffff || opt->max_matesw < 0 ||
+        opt->mask_level_redun != opt->mask_level_redun)
+        return fail(SMEM_E_ARG, "smem_matesw: scoring needs e >= 1, o >= 0, a >= 1, 0 <= min_seed_len * a < 65536");
+    if (kernel_ms) *kernel_ms = 0.0;
+    *n_regs_out = 0;
+    reg_off_out[0] = 0;
+    if (n_pairs == 0) return SMEM_OK;
+    const size_t n_reads = 2 * (size_t)n_pairs;
+    if (offs[0] != 0 || reg_off[0] != 0) return fail(SMEM_E_ARG, "smem_matesw: offsets start at 0");
+    for (size_t r = 0; r < n_reads; ++r)
+        if (offs[r + 1] < offs[r] || offs[r + 1] - offs[r] > (1u << 30) || reg_off[r + 1] < reg_off[r])
+            return fail(SMEM_E_ARG, "smem_matesw: offsets not ascending");
+    const uint64_t n_bases = offs[n_reads], n_regs = reg_off[n_reads];
+    if (n_regs >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_matesw: too many regions");
+    if (n_regs > 0 && !regs) return fail(SMEM_E_ARG, "smem_matesw: no regions");
+    for (uint64_t k = 0; k < n_bases; ++k)
+        if (codes[k] > 4) return fail(SMEM_E_ARG, "smem_matesw: code > 4");
+    // work space: read r's list grows by at most four regions per mem_matesw call on it, one call per
+    // anchor of the other end; two buffers of that size (an insertion or a sort writes the other one)
+    std::vector<uint64_t> woff(n_reads + 1);
+    std::vector<uint32_t> n_anchor(n_reads);
+    for (size_t r = 0; r < n_reads; ++r) {
+        const int64_t l_query = (int64_t)(offs[r + 1] - offs[r]);
+        uint32_t na = 0;
+        for (uint64_t k = reg_off[r]; k < reg_off[r + 1]; ++k) {
+            const smem_alnreg_t& R = regs[k];
+            if (R.qb < 0 || R.qe > l_query || R.qe <= R.qb || R.rb < 0 || R.re < R.rb || R.re > 2 * l_pac)
+                return fail(SMEM_E_ARG, "smem_matesw: region outside its read or the reference");
+            if ((int64_t)R.score >= (int64_t)regs[reg_off[r]].score - opt->pen_unpaired) ++na;
+        }
+        n_anchor[r] = std::min<uint32_t>(na, (uint32_t)opt->max_matesw);
+    }
+    woff[0] = 0;
+    for (size_t r = 0; r < n_reads; ++r) {
+        const uint64_t n = reg_off[r + 1] - reg_off[r];
+        const uint64_t cap = std::max<uint64_t>(n, std::min<uint64_t>(smem::FIN_MAX_REGS, n + 4ull * n_anchor[r ^ 1]));
+        woff[r + 1] = woff[r] + 2 * cap;
+    }
+    if (woff[n_reads] >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_matesw: too many anchors");
+    DevBuf<uint8_t> dcodes, dpac, dsrc;
+    DevBuf<smem::AlnReg> dregs, dwork, dout;
+    DevBuf<uint64_t> doffs, dregoff, dwoff, dnout, doutoff;
+    DevBuf<uint32_t> dctr, dlist;
+    DevBuf<int32_t> dnsw, dstatus;
+    HostBuf<uint64_t> hnout;   // pinned: the per-read counts come back while the stream runs on
+    Events<4> ev;
+    DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
+    if (call.rc) return call.rc;
+    const hipStream_t st = call.st;
+    HIP_TRY(ev.create());
+    const uint64_t pac_bytes = (uint64_t)(l_pac + 3) / 4;
+    HIP_TRY(dcodes.ensure(n_bases + 64));
+    if (pac) HIP_TRY(dpac.ensure(pac_bytes + 64));
+    HIP_TRY(dregs.ensure(n_regs));
+    HIP_TRY(dwork.ensure(woff[n_reads]));
+    HIP_TRY(doffs.ensure(n_reads + 1));
+    HIP_TRY(dregoff.ensure(n_reads + 1));
+    HIP_TRY(dwoff.ensure(n_reads + 1));
+    HIP_TRY(dnout.ensure(n_reads));
+    HIP_TRY(doutoff.ensure(n_reads + 1));
+    HIP_TRY(dsrc.ensure(n_reads));
+    HIP_TRY(dctr.ensure(4));
+    HIP_TRY(dlist.ensure((size_t)n_pairs));
+    HIP_TRY(dnsw.ensure((size_t)n_pairs));
+    HIP_TRY(dstatus.ensure((size_t)n_pairs));
+    HIP_TRY(hnout.ensure(n_reads + 1));
+    if (n_bases) HIP_TRY(hipMemcpyAsync(dcodes.p, codes, n_bases, hipMemcpyHostToDevice, st));
+    if (pac) HIP_TRY(hipMemcpyAsync(dpac.p, pac, pac_bytes, hipMemcpyHostToDevice, st));
+    if (n_regs) HIP_TRY(hipMemcpyAsync(dregs.p, regs, sizeof(smem::AlnReg) * n_regs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(doffs.p, offs, 8 * (n_reads + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dregoff.p, reg_off, 8 * (n_reads + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dwoff.p, woff.data(), 8 * (n_reads + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dctr.p, 0, sizeof(uint32_t) * 4, st));
+    smem::MswParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.codes = dcodes.p, P.offs = doffs.p, P.regs = dregs.p, P.reg_off = dregoff.p;
+    P.pac = pac ? dpac.p : g->d_pac, P.l_pac = l_pac, P.n_pairs = n_pairs;
+    for (int r = 0; r < 4; ++r) P.pes[r] = smem::MswPes{pes[r].low, pes[r].high, pes[r].failed};
+    std::memcpy(P.mat, opt->sc.mat, 25);
+    P.o_del = opt->sc.o_del, P.e_del = opt->sc.e_del, P.o_ins = opt->sc.o_ins, P.e_ins = opt->sc.e_ins;
+    P.a = opt->a, P.min_seed_len = opt->min_seed_len, P.pen_unpaired = opt->pen_unpaired, P.max_matesw = opt->max_matesw;
+    P.mask_level_redun = opt->mask_level_redun;
+    {  // ksw_qinit's bias and largest score (software/ksw.c:78-85)
+        uint8_t sh = 127, md = 0;
+        for (int k = 0; k < 25; ++k) {
+            if (opt->sc.mat[k] < (int8_t)sh) sh = (uint8_t)opt->sc.mat[k];
+            if (opt->sc.mat[k] > (int8_t)md) md = (uint8_t)opt->sc.mat[k];
+        }
+        P.top = md, P.shift = (uint8_t)(256 - sh);
+    }
+    P.work = dwork.p, P.woff = dwoff.p, P.ctr = dctr.p, P.wave_list = dlist.p, P.n_out = dnout.p, P.src = dsrc.p;
+    P.n_sw = dnsw.p, P.status = dstatus.p, P.out_off = doutoff.p;
+    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(smem_launch_msw_pre(&P, st));
+    HIP_TRY(smem_launch_msw_wave(&P, g->n_cu, st));
+    HIP_TRY(hipEventRecord(ev[1], st));
+    HIP_TRY(hipMemcpyAsync(hnout.p, dnout.p, 8 * n_reads, hipMemcpyDeviceToHost, st));
+    INJECT(ST_MSW);
+    HIP_TRY(hipStreamSynchronize(st));
+    uint64_t total = 0;
+    for (size_t r = 0; r < n_reads; ++r) {
+        if (hnout.p[r] > (uint64_t)smem::FIN_MAX_REGS && hnout.p[r] != reg_off[r + 1] - reg_off[r])
+            return fail(SMEM_E_INTERNAL, "smem_matesw: a list past its limit");
+        reg_off_out[r] = total;
+        total += hnout.p[r];
+    }
+    reg_off_out[n_reads] = total;
+    *n_regs_out = total;
+    HIP_TRY(hipMemcpyAsync(n_sw, dnsw.p, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(status, dstatus.p, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+    if (total > regs_cap) {
+        HIP_TRY(hipStreamSynchronize(st));
+        return fail(SMEM_E_CAPACITY, "smem_matesw: regs_out too small (n_regs_out holds the size needed)");
+    }
+    HIP_TRY(dout.ensure(total));
+    HIP_TRY(hipMemcpyAsync(doutoff.p, reg_off_out, 8 * (n_reads + 1), hipMemcpyHostToDevice, st));
+    P.out = dout.p;
+    HIP_TRY(hipEventRecord(ev[2], st));
+    HIP_TRY(smem_launch_msw_write(&P, total, st));
+    HIP_TRY(hipEventRecord(ev[3], st));
+    if (total) HIP_TRY(hipMemcpyAsync(regs_out, dout.p, sizeof(smem::AlnReg) * total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f, ms2 = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms2, ev[2], ev[3]));
+    if (kernel_ms) *kernel_ms = (double)ms + (double)ms2;
     return SMEM_OK;
 }
 

@@ -44,6 +44,7 @@ EXPORTED = [
     "smem_gpu_load_contigs", "smem_batch_reg2aln", "smem_batch_aln2_results",
     "smem_gpu_load_contig_names", "smem_batch_set_read_text", "smem_batch_sam", "smem_batch_sam_results",
     "smem_sam_text", "smem_batch_sam_stats",
+    "smem_ksw_align2_long", "smem_matesw_opt_default", "smem_matesw",
 ]
 
 # smem_batch_fetch_mask bits (include/smem_gpu.h)
@@ -51,6 +52,7 @@ FETCH_INTV, FETCH_SA, FETCH_CHAINS, FETCH_REGS, FETCH_ALL = 1, 2, 4, 8, 15
 FETCH_FIN = 16   # Batch.reg_finalize's results; not part of FETCH_ALL
 FETCH_ALN = 32   # Batch.reg2aln's results; not part of FETCH_ALL
 FETCH_SAM = 64   # Batch.sam's text; not part of FETCH_ALL
+KSWA_MAX_TLEN = 2048   # SMEM_KSWA_MAX_TLEN: the longest target of Gpu.ksw_align2_long
 COLLECT_NO_FETCH = 1
 
 
@@ -188,6 +190,37 @@ def fin_opt(**kw) -> FinOptT:
     return o
 
 
+class PestatT(C.Structure):
+    """smem_pestat_t = mem_pestat_t"""
+    _fields_ = [("low", C.c_int32), ("high", C.c_int32), ("failed", C.c_int32), ("pad", C.c_int32),
+                ("avg", C.c_double), ("std", C.c_double)]
+
+
+class MateswOptT(C.Structure):
+    """smem_matesw_opt_t: the mem_opt_t fields mate rescue reads"""
+    _fields_ = [("mat", C.c_int8 * 25), ("pad", C.c_int8 * 3), ("o_del", C.c_int32), ("e_del", C.c_int32),
+                ("o_ins", C.c_int32), ("e_ins", C.c_int32), ("a", C.c_int32), ("min_seed_len", C.c_int32),
+                ("pen_unpaired", C.c_int32), ("max_matesw", C.c_int32), ("mask_level_redun", C.c_float),
+                ("pad2", C.c_int32)]
+
+
+MSW_HOST = 1   # SMEM_MSW_HOST: the pair is the caller's
+
+
+def matesw_opt(**kw) -> MateswOptT:
+    """smem_matesw_opt_default (mem_opt_init, software/bwamem.c:48-75) with the named fields
+    overridden; mat takes the 25 entries of a scoring matrix (synth.bwa_scmat)."""
+    o = MateswOptT()
+    load().smem_matesw_opt_default(C.byref(o))
+    for k, v in kw.items():
+        if k == "mat":
+            for i, x in enumerate(np.asarray(v, dtype=np.int8).reshape(-1)[:25]):
+                o.mat[i] = int(x)
+        else:
+            setattr(o, k, v)
+    return o
+
+
 SEED_DT = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4")])          # smem_seed_t = mem_seed_t
 CHAIN_DT = np.dtype([("pos", "<i8"), ("seed_off", "<u8"), ("n", "<i4"), ("pad", "<i4")])  # smem_chain_t
 # smem_alnreg_t = mem_alnreg_t (the 64-byte records chain2aln returns)
@@ -306,6 +339,12 @@ def load() -> C.CDLL:
                                          C.c_int, C.c_void_p, C.c_void_p, P(StreamStats)]
     lib.smem_ksw_align2.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                     P(KswOptT), C.c_void_p, P(C.c_double)]
+    lib.smem_ksw_align2_long.argtypes = lib.smem_ksw_align2.argtypes
+    lib.smem_matesw_opt_default.argtypes = [P(MateswOptT)]
+    lib.smem_matesw_opt_default.restype = None
+    lib.smem_matesw.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_int64, P(MateswOptT), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                C.c_void_p, P(C.c_uint64), P(C.c_double)]
     lib.smem_gpu_load_pac.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.smem_batch_chain2aln.argtypes = [C.c_void_p, C.c_void_p]
     lib.smem_batch_aln_results.argtypes = [C.c_void_p, P(C.c_void_p), P(P(C.c_uint64)), P(C.c_uint64)]
@@ -781,6 +820,14 @@ class Gpu:
     def ksw_align2(self, kb) -> tuple:
         """ksw_align2 (software/ksw.c:342) of every KSWA_TASK of a synth.KswBatch
         on this device: (results as synth.KSWA_RESULT, kernel ms)."""
+        return self._ksw_align2(kb, "smem_ksw_align2")
+
+    def ksw_align2_long(self, kb) -> tuple:
+        """ksw_align2 with targets of up to KSWA_MAX_TLEN bases, mem_matesw's windows
+        (smem_ksw_align2_long): (results as synth.KSWA_RESULT, kernel ms)."""
+        return self._ksw_align2(kb, "smem_ksw_align2_long")
+
+    def _ksw_align2(self, kb, entry: str) -> tuple:
         from . import synth
         lib = load()
         tasks = np.ascontiguousarray(kb.tasks, dtype=synth.KSWA_TASK)
@@ -792,9 +839,62 @@ class Gpu:
         o.o_del, o.e_del, o.o_ins, o.e_ins = kb.o_del, kb.e_del, kb.o_ins, kb.e_ins
         out = np.zeros(max(tasks.size, 1), dtype=synth.KSWA_RESULT)
         ms = C.c_double()
-        _check(lib.smem_ksw_align2(self._h, tasks.size, tasks.ctypes.data, q.ctypes.data, q.size, t.ctypes.data,
-                                   t.size, C.byref(o), out.ctypes.data, C.byref(ms)), "smem_ksw_align2")
+        _check(getattr(lib, entry)(self._h, tasks.size, tasks.ctypes.data, q.ctypes.data, q.size, t.ctypes.data,
+                                   t.size, C.byref(o), out.ctypes.data, C.byref(ms)), entry)
         return out[:tasks.size], ms.value
+
+    def matesw(self, pac, l_pac: int, codes, offs, regs, reg_off, pes, opt: "MateswOptT" = None,
+               regs_cap: int | None = None, grow: bool = True) -> tuple:
+        """The rescue loop of mem_sam_pe (software/bwamem_pair.c:252-263) of every pair on this
+        device (smem_matesw): reads 2p and 2p + 1 are pair p, regs (ALNREG_DT) / reg_off each
+        read's regions, pes four (low, high, failed) tuples or PestatT, pac None: the resident
+        one.  Returns (regions as ALNREG_DT, reg_off_out, n_sw, status, kernel ms).  The output
+        starts at regs_cap regions (default: a guess) and the call is repeated with the size the
+        library reports when that is too small (grow=False: SmemError with .n_regs instead)."""
+        lib = load()
+        if pac is not None:
+            pac = np.ascontiguousarray(pac, dtype=np.uint8)
+            if pac.size < (int(l_pac) + 3) // 4:
+                raise SmemError("matesw: pac holds fewer than (l_pac + 3) / 4 bytes")
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.uint64)
+        regs = np.ascontiguousarray(regs)
+        if regs.dtype != ALNREG_DT:
+            regs = np.frombuffer(regs.astype(np.uint8, copy=False).tobytes(), dtype=ALNREG_DT)
+        if offs.size < 1 or offs.size % 2 != 1 or reg_off.size != offs.size:
+            raise SmemError("matesw: offs and reg_off need 2 n_pairs + 1 entries")
+        if int(reg_off[-1]) > regs.size or int(offs[-1]) > codes.size:
+            raise SmemError("matesw: offsets end past their arrays")
+        n_pairs = (offs.size - 1) // 2
+        pe = (PestatT * 4)()
+        for r in range(4):
+            if isinstance(pes[r], PestatT):
+                pe[r] = pes[r]
+            else:
+                pe[r].low, pe[r].high, pe[r].failed = (int(x) for x in pes[r][:3])
+        if opt is None:
+            opt = matesw_opt()
+        cap = int(regs_cap) if regs_cap is not None else int(reg_off[-1]) + 2 * n_pairs + 16
+        reg_off_out = np.zeros(2 * n_pairs + 1, dtype=np.uint64)
+        n_sw = np.zeros(max(n_pairs, 1), dtype=np.int32)
+        status = np.zeros(max(n_pairs, 1), dtype=np.int32)
+        ms, need = C.c_double(), C.c_uint64()
+        while True:
+            out = np.zeros(max(cap, 1), dtype=ALNREG_DT)
+            rc = lib.smem_matesw(self._h, n_pairs, codes.ctypes.data, offs.ctypes.data, regs.ctypes.data,
+                                 reg_off.ctypes.data, C.cast(pe, C.c_void_p), pac.ctypes.data if pac is not None else None,
+                                 int(l_pac), C.byref(opt), out.ctypes.data, cap, reg_off_out.ctypes.data,
+                                 n_sw.ctypes.data, status.ctypes.data, C.byref(need), C.byref(ms))
+            if rc == SMEM_E_CAPACITY and need.value > cap and grow:
+                cap = int(need.value)
+                continue
+            if rc == SMEM_E_CAPACITY and need.value > cap:
+                err = SmemError(f"smem_matesw failed: SMEM_E_CAPACITY: the lists need {need.value} regions")
+                err.n_regs = int(need.value)
+                raise err
+            _check(rc, "smem_matesw")
+            return out[:int(need.value)], reg_off_out, n_sw[:n_pairs], status[:n_pairs], ms.value
 
     def load_pac(self, pac, l_pac: int) -> None:
         """Keep the 2-bit .pac resident in HBM (smem_gpu_load_pac)."""

@@ -28,7 +28,7 @@
  * caller that takes its CPU path on SMEM_E_DEVICE computes exactly what the
  * reference computes.  Allocation failures are SMEM_E_NOMEM and leave the
  * device usable.  SMEM_GPU_FAIL=<stage>:<k>[:sticky] (stage: upload, seed,
- * sa, chain, aln, fin, g2a, sam, fetch, any) injects SMEM_E_DEVICE into every k-th
+ * sa, chain, aln, fin, g2a, sam, matesw, fetch, any) injects SMEM_E_DEVICE into every k-th
  * call of the stage after its work is enqueued, to test that contract.
  */
 #ifndef SMEM_GPU_H
@@ -441,6 +441,15 @@ typedef struct {
 int  smem_ksw_align2(smem_gpu_t *gpu, int n, const smem_ksw_atask_t *tasks, const uint8_t *q, uint64_t q_bytes,
                      const uint8_t *t, uint64_t t_bytes, const smem_ksw_opt_t *opt, smem_ksw_aresult_t *out,
                      double *kernel_ms);
+/* The same call for the targets mem_matesw builds (software/bwamem_pair.c:144: a window of
+ * several hundred to a few thousand reference bases): 1 <= qlen <= 256, 0 <= tlen <=
+ * SMEM_KSWA_MAX_TLEN, anything else SMEM_E_ARG before any device work.  One wave per problem;
+ * the target is fetched 64 rows at a time and the suboptimal list, up to tlen / 2 + 1 entries,
+ * is kept in LDS (8200 B a wave).  Every kswr_t field is the reference's. */
+#define SMEM_KSWA_MAX_TLEN 2048
+int  smem_ksw_align2_long(smem_gpu_t *gpu, int n, const smem_ksw_atask_t *tasks, const uint8_t *q, uint64_t q_bytes,
+                          const uint8_t *t, uint64_t t_bytes, const smem_ksw_opt_t *opt, smem_ksw_aresult_t *out,
+                          double *kernel_ms);
 
 /* ------------------------------------------- chains -> alignment regions */
 /* mem_alnreg_t (software/bwamem.h:62-74); hash / sub / sub_n / secondary are
@@ -625,6 +634,46 @@ int  smem_batch_reg_finalize(smem_batch_t *b, const int64_t *ids, int64_t id0, c
 int  smem_batch_fin_results(const smem_batch_t *b, const smem_alnreg_t **regs_out, const uint64_t **out_off,
                             const smem_fin_sel_t **sel, const uint64_t **sel_idx, const uint64_t **sel_off,
                             const int32_t **status, uint64_t *n_out, uint64_t *n_sel);
+
+/* ------------------------------------------------------------ mate rescue */
+/* The rescue loop of mem_sam_pe (software/bwamem_pair.c:252-263): for the good hits of either
+ * end -- score >= the end's first region's score - pen_unpaired, at most max_matesw of them,
+ * taken from the lists as they come in -- mem_matesw (:109-175) of the other end's read: a
+ * ksw_align2 of the mate against the window the insert-size bounds give, in every orientation
+ * that has not failed and that no region of the mate's current list already fills, the hit
+ * inserted before the first lower score, then mem_sort_and_dedup.  End 0's anchors change end 1's
+ * list; end 1's anchors then change end 0's.
+ * mem_pestat_t (software/bwamem.h:78-82); the stage reads low, high and failed, which the caller
+ * computes (mem_pestat stays on the host). */
+typedef struct {
+	int32_t low, high, failed, pad;
+	double avg, std;
+} smem_pestat_t;
+typedef struct {
+	smem_ksw_opt_t sc;        /* matrix and gap penalties */
+	int32_t a, min_seed_len;
+	int32_t pen_unpaired;     /* 17 */
+	int32_t max_matesw;       /* 100 */
+	float mask_level_redun;   /* 0.95 */
+	int32_t pad;
+} smem_matesw_opt_t;
+void smem_matesw_opt_default(smem_matesw_opt_t *opt);
+#define SMEM_MSW_HOST 1
+/* Host buffers in and out.  Reads 2p and 2p + 1 are pair p: codes (0..4) / offs[2 n_pairs + 1];
+ * regs / reg_off[2 n_pairs + 1] are each read's regions as mem_align1_core leaves them (after
+ * mem_sort_and_dedup), 0 <= qb < qe <= the read's length; pac NULL: the resident .pac of this
+ * l_pac.  regs_out (room for regs_cap regions) / reg_off_out[2 n_pairs + 1] get both ends' lists
+ * after the loop, n_sw[p] the n mem_sam_pe accumulates from mem_matesw's return values,
+ * status[p] 0 or SMEM_MSW_HOST, *n_regs_out the regions written.  SMEM_MSW_HOST: the pair is
+ * left to the caller's CPU path, its lists copied through and n_sw 0 -- a mate of 0 or more than
+ * 256 bp, a list of more than SMEM_FIN_MAX_REGS regions (coming in, or after an insertion), or an
+ * SW window longer than SMEM_KSWA_MAX_TLEN.  SMEM_E_CAPACITY when regs_cap is too small:
+ * *n_regs_out is the size to come back with.  SMEM_E_ARG: offsets that do not ascend, a code
+ * above 4, a region outside its read, no .pac, gap penalties with e < 1 or o < 0, a < 1. */
+int  smem_matesw(smem_gpu_t *gpu, int n_pairs, const uint8_t *codes, const uint64_t *offs, const smem_alnreg_t *regs,
+                 const uint64_t *reg_off, const smem_pestat_t pes[4], const uint8_t *pac, int64_t l_pac,
+                 const smem_matesw_opt_t *opt, smem_alnreg_t *regs_out, uint64_t regs_cap, uint64_t *reg_off_out,
+                 int32_t *n_sw, int32_t *status, uint64_t *n_regs_out, double *kernel_ms);
 
 /* ------------------------------------------- alignments -> SAM text */
 /* The text mem_reg2sam_se(opt, bns, pac, s, a, 0, 0) leaves in s->sam (software/bwamem.c:1359-1393,
