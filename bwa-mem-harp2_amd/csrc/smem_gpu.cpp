@@ -1056,6 +1056,14 @@ int smem_gpu_grid_reads(const smem_gpu_t* g) {
     return (int)((int64_t)n_cu * lpc / 64 * seed_owners_per_wave(g->variant));
 }
 
+int smem_gpu_cu_count(const smem_gpu_t* g) {
+    if (!g) return SMEM_E_ARG;
+    int n_cu = g->n_cu;
+    if (n_cu <= 0 && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess)
+        return SMEM_E_DEVICE;
+    return n_cu;
+}
+
 // D of a table's per-level minimum sizes mn[1..k]: the largest level D < k such that no string of
 // D + 1 bases is absent (every level up to D + 1 is then complete: a level's minimum is at most the
 // one before it).  Up to D bases every extension of a present string is strictly smaller.

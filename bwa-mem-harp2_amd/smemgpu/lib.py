@@ -44,7 +44,7 @@ EXPORTED = [
     "smem_gpu_load_contigs", "smem_batch_reg2aln", "smem_batch_aln2_results",
     "smem_gpu_load_contig_names", "smem_batch_set_read_text", "smem_batch_sam", "smem_batch_sam_results",
     "smem_sam_text", "smem_batch_sam_stats",
-    "smem_ksw_align2_long", "smem_matesw_opt_default", "smem_matesw",
+    "smem_ksw_align2_long", "smem_matesw_opt_default", "smem_matesw", "smem_gpu_cu_count",
 ]
 
 # smem_batch_fetch_mask bits (include/smem_gpu.h)
@@ -367,6 +367,9 @@ def load() -> C.CDLL:
     lib.smem_gpu_get_kernel_variant.restype = C.c_int
     lib.smem_gpu_grid_reads.argtypes = [C.c_void_p]
     lib.smem_gpu_grid_reads.restype = C.c_int
+    if hasattr(lib, "smem_gpu_cu_count"):  # absent from A/B libraries built before it
+        lib.smem_gpu_cu_count.argtypes = [C.c_void_p]
+        lib.smem_gpu_cu_count.restype = C.c_int
     lib.smem_gpu_set_kmer_table.argtypes = [C.c_void_p, C.c_int]
     if hasattr(lib, "smem_gpu_kmer_facts"):  # absent from A/B libraries built before the virtual entries
         lib.smem_gpu_kmer_facts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_int]
@@ -695,6 +698,16 @@ class Gpu:
     def grid_reads(self) -> int:
         """Reads one seeding launch holds in flight (smem_gpu_grid_reads)."""
         return int(load().smem_gpu_grid_reads(self._h))
+
+    def cu_count(self) -> int:
+        """The device's compute units (smem_gpu_cu_count)."""
+        lib = load()
+        if not hasattr(lib, "smem_gpu_cu_count"):
+            raise SmemError("smem_gpu_cu_count: this library was built before it")
+        n = int(lib.smem_gpu_cu_count(self._h))
+        if n < 1:
+            raise SmemError(f"smem_gpu_cu_count failed: {n}")
+        return n
 
     @property
     def variant(self) -> int:

@@ -215,6 +215,10 @@ int  smem_gpu_reserve_slots(smem_gpu_t *gpu, int n_slots, int reads_per_slot, in
  * many reads fills the device by itself (the binding's batch plan).
  * Needs no open device work: the CU count comes from the device's attributes. */
 int  smem_gpu_grid_reads(const smem_gpu_t *gpu);
+/* The device's compute units, by which the stages size their grids (mate
+ * rescue's wave kernel: MSW_WAVES_PER_CU waves each, csrc/matesw_kernels.h);
+ * < 0 on error. */
+int  smem_gpu_cu_count(const smem_gpu_t *gpu);
 /* Admission, the HARP manager's role (software/fastmap.c:320-429): at most n
  * calls run work on the device at once, each on one of n leased stream pairs
  * (a device carries at most 2n streams however many workers share it); the

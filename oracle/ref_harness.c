@@ -43,6 +43,19 @@
  *       the reference's own ksw_align2 (software/ksw.c:342) on every task
  *       (SMAT: as SMKT with per task {u64 q_off, t_off; i32 qlen, tlen, xtra, pad}),
  *       results as SMAR: "SMAR0001", u64 n, n x i32 {score, te, qe, score2, te2, tb, qb}.
+ *   msw   <in.smmi> <out.smmo>
+ *       the reference's own mem_matesw (software/bwamem_pair.c:109) on given lists, driven
+ *       per pair as mem_sam_pe drives it (:252-263): each end's regions within
+ *       pen_unpaired of its first are copied, the first max_matesw of them rescue the
+ *       other end, end 0's first, and the returns are summed.  No limit on mate
+ *       length, window or list length.
+ *       SMMI: "SMMI0001", i64 l_pac, i32 pes[4] x {low, high, failed},
+ *       i32 {a, b, o_del, e_del, o_ins, e_ins, min_seed_len, pen_unpaired, max_matesw, 0},
+ *       f32 mask_level_redun, u64 {n_pairs, n_pac, n_codes, n_regs}, the .pac bytes,
+ *       the reads' codes, u64 offs[2 n_pairs + 1], u64 reg_off[2 n_pairs + 1], n_regs x
+ *       {i64 rb, re; i32 qb, qe, score, truesc, sub, csub, sub_n, w, seedcov, secondary; u64 hash}.
+ *       SMMO: "SMMO0001", u64 n_pairs, u64 n_regs, i32 n[n_pairs] (the summed returns),
+ *       u64 reg_off[2 n_pairs + 1], the lists afterwards as n_regs regions.
  *   mem   <prefix> <reads.fq> <n_threads> <batch_size> <pe> [<pg> [-k|-w|-A|-B|-O|-E|-L|-d <value>]...]
  *       The body of the reference's main_mem (software/fastmap.c:193-230) on the
  *       unmodified pipeline: bwa_print_sam_hdr, then bseq_read chunks through
@@ -505,6 +518,118 @@ static int cmd_kswa(int argc, char **argv)
 	return 0;
 }
 
+/* msw <in.smmi> <out.smmo>: the reference's own mem_matesw on given lists */
+extern int mem_matesw(const mem_opt_t *opt, int64_t l_pac, const uint8_t *pac, const mem_pestat_t pes[4],
+		const mem_alnreg_t *a, int l_ms, const uint8_t *ms, mem_alnreg_v *ma);
+
+/* a region as the files hold it: the fields of tests/regfin_ref.py's FIELDS, 64 bytes */
+typedef struct { int64_t rb, re; int32_t v[10]; uint64_t hash; } msw_reg_t;
+
+static void msw_to_ref(const msw_reg_t *s, mem_alnreg_t *d)
+{
+	memset(d, 0, sizeof(*d));
+	d->rb = s->rb; d->re = s->re;
+	d->qb = s->v[0]; d->qe = s->v[1]; d->score = s->v[2]; d->truesc = s->v[3]; d->sub = s->v[4]; d->csub = s->v[5];
+	d->sub_n = s->v[6]; d->w = s->v[7]; d->seedcov = s->v[8]; d->secondary = s->v[9];
+	d->hash = s->hash;
+}
+
+static void msw_from_ref(const mem_alnreg_t *a, msw_reg_t *d)
+{
+	int32_t v[10] = { a->qb, a->qe, a->score, a->truesc, a->sub, a->csub, a->sub_n, a->w, a->seedcov, a->secondary };
+	d->rb = a->rb; d->re = a->re;
+	memcpy(d->v, v, sizeof(v));
+	d->hash = a->hash;
+}
+
+static int cmd_msw(int argc, char **argv)
+{
+	char magic[8];
+	int64_t l_pac;
+	int32_t pe[12], o[10];
+	float mask_level_redun;
+	uint64_t cnt[4], n_pairs, n_pac, n_codes, n_regs, p, n_out = 0, m_out = 0;
+	uint8_t *pac, *codes;
+	uint64_t *offs, *reg_off, *out_off;
+	msw_reg_t *regs, *out = 0;
+	int32_t *n_sw;
+	mem_opt_t *opt;
+	mem_pestat_t pes[4];
+	FILE *fp;
+	int r;
+	if (argc < 3) { fprintf(stderr, "usage: msw <in.smmi> <out.smmo>\n"); return 1; }
+	fp = fopen(argv[1], "rb");
+	if (!fp) return 1;
+	if (fread(magic, 1, 8, fp) != 8 || memcmp(magic, "SMMI0001", 8) != 0) return 1;
+	if (fread(&l_pac, 8, 1, fp) != 1 || fread(pe, 4, 12, fp) != 12 || fread(o, 4, 10, fp) != 10) return 1;
+	if (fread(&mask_level_redun, 4, 1, fp) != 1 || fread(cnt, 8, 4, fp) != 4) return 1;
+	n_pairs = cnt[0]; n_pac = cnt[1]; n_codes = cnt[2]; n_regs = cnt[3];
+	if (l_pac < 1 || n_pac < (uint64_t)(l_pac + 3) / 4) return 1;
+	pac = calloc(n_pac + 1, 1);
+	codes = malloc(n_codes ? n_codes : 1);
+	offs = malloc(8 * (2 * n_pairs + 1));
+	reg_off = malloc(8 * (2 * n_pairs + 1));
+	out_off = malloc(8 * (2 * n_pairs + 1));
+	regs = malloc(sizeof(msw_reg_t) * (n_regs ? n_regs : 1));
+	n_sw = malloc(4 * (n_pairs ? n_pairs : 1));
+	if (fread(pac, 1, n_pac, fp) != n_pac || fread(codes, 1, n_codes, fp) != n_codes) return 1;
+	if (fread(offs, 8, 2 * n_pairs + 1, fp) != 2 * n_pairs + 1) return 1;
+	if (fread(reg_off, 8, 2 * n_pairs + 1, fp) != 2 * n_pairs + 1) return 1;
+	if (fread(regs, sizeof(msw_reg_t), n_regs, fp) != n_regs) return 1;
+	fclose(fp);
+	if (offs[2 * n_pairs] > n_codes || reg_off[2 * n_pairs] > n_regs) return 1;
+	opt = mem_opt_init();
+	opt->a = o[0]; opt->b = o[1];
+	opt->o_del = o[2]; opt->e_del = o[3]; opt->o_ins = o[4]; opt->e_ins = o[5];
+	opt->min_seed_len = o[6]; opt->pen_unpaired = o[7]; opt->max_matesw = o[8];
+	opt->mask_level_redun = mask_level_redun;
+	bwa_fill_scmat(opt->a, opt->b, opt->mat);
+	memset(pes, 0, sizeof(pes));
+	for (r = 0; r < 4; ++r) pes[r].low = pe[3 * r], pes[r].high = pe[3 * r + 1], pes[r].failed = pe[3 * r + 2];
+	out_off[0] = 0;
+	for (p = 0; p < n_pairs; ++p) {
+		mem_alnreg_v a[2], b[2];
+		int e, j, n = 0;
+		for (e = 0; e < 2; ++e) {   /* the pair's lists, and of each the good hits as they came */
+			uint64_t lo = reg_off[2 * p + e], k, cnt_e = reg_off[2 * p + e + 1] - lo;
+			a[e].n = a[e].m = cnt_e; a[e].a = malloc(sizeof(mem_alnreg_t) * (cnt_e ? cnt_e : 1));
+			b[e].n = 0; b[e].m = cnt_e; b[e].a = malloc(sizeof(mem_alnreg_t) * (cnt_e ? cnt_e : 1));
+			for (k = 0; k < cnt_e; ++k) msw_to_ref(&regs[lo + k], &a[e].a[k]);
+			for (k = 0; k < cnt_e; ++k)
+				if (a[e].a[k].score >= a[e].a[0].score - opt->pen_unpaired) b[e].a[b[e].n++] = a[e].a[k];
+		}
+		for (e = 0; e < 2; ++e) {   /* end e's hits rescue the other end, end 0's first */
+			const int m = 1 - e;
+			for (j = 0; j < (int)b[e].n && j < opt->max_matesw; ++j)
+				n += mem_matesw(opt, l_pac, pac, pes, &b[e].a[j], (int)(offs[2 * p + m + 1] - offs[2 * p + m]),
+						codes + offs[2 * p + m], &a[m]);
+		}
+		n_sw[p] = n;
+		for (e = 0; e < 2; ++e) {
+			uint64_t k;
+			if (n_out + a[e].n > m_out) {
+				m_out = (n_out + a[e].n) * 2 + 16;
+				out = realloc(out, sizeof(msw_reg_t) * m_out);
+			}
+			for (k = 0; k < a[e].n; ++k) msw_from_ref(&a[e].a[k], &out[n_out + k]);
+			n_out += a[e].n;
+			out_off[2 * p + e + 1] = n_out;
+			free(a[e].a); free(b[e].a);
+		}
+	}
+	fp = fopen(argv[2], "wb");
+	if (!fp) return 1;
+	fwrite("SMMO0001", 1, 8, fp);
+	fwrite(&n_pairs, 8, 1, fp);
+	fwrite(&n_out, 8, 1, fp);
+	fwrite(n_sw, 4, n_pairs, fp);
+	fwrite(out_off, 8, 2 * n_pairs + 1, fp);
+	fwrite(out, sizeof(msw_reg_t), n_out, fp);
+	fclose(fp);
+	free(pac); free(codes); free(offs); free(reg_off); free(out_off); free(regs); free(n_sw); free(out); free(opt);
+	return 0;
+}
+
 /* the HARP-path globals of software/fastmap.c:27-29 and software/main.c:28 (their
  * definitions are linked from the reference objects; allocated here as
  * main_mem and the manager thread do) */
@@ -643,6 +768,7 @@ int main(int argc, char **argv)
 	if (strcmp(argv[1], "aln") == 0) return cmd_aln(argc - 1, argv + 1);
 	if (strcmp(argv[1], "mem") == 0) return cmd_mem(argc - 1, argv + 1);
 	if (strcmp(argv[1], "kswa") == 0) return cmd_kswa(argc - 1, argv + 1);
+	if (strcmp(argv[1], "msw") == 0) return cmd_msw(argc - 1, argv + 1);
 	fprintf(stderr, "unknown command %s\n", argv[1]);
 	return 1;
 }

@@ -1,9 +1,10 @@
 """Golden data for mate rescue (mem_matesw, software/bwamem_pair.c:109-175):
 the long-target ksw_align2 problems and one paired-end set.
 
-    python tests/golden/make_golden_msw.py              # both
+    python tests/golden/make_golden_msw.py              # all three
     python tests/golden/make_golden_msw.py --kswa-only
     python tests/golden/make_golden_msw.py --pairs-only
+    python tests/golden/make_golden_msw.py --hand-only
 
   kswa_msw_a<1|2>.smat.gz / .smar.gz
         ksw_align2 problems with targets of 257..MAX_TLEN bases under
@@ -18,6 +19,19 @@ the long-target ksw_align2 problems and one paired-end set.
         (ref_harness mem ... 1), its regions of every read before
         mem_sort_and_dedup (ref_harness aln) and what it printed about insert
         sizes: the proper-pair bounds of FR and the orientations it skipped
+  msw/hand/<batch>.smmo.gz, msw/hand/manifest.json
+        the reference's own mem_matesw (ref_harness msw: the loop of
+        software/bwamem_pair.c:252-263 around it) on every hand-built batch of
+        tests/matesw_data.fixtures(): each read's list afterwards and the summed
+        returns per pair (SMMO, oracle/ref_harness.c).  The inputs are not stored:
+        the manifest names the builder, the bounds, the options, the pair count and
+        the sha256 of the harness's input, which tests/test_matesw.py recomputes
+        from the builders.  Batches:
+          all_<o>, fr_<o>      build (PES_ALL) and build_fr (PES_FR) under
+                               o = base, a2, one_anchor, no_margin, no_anchor
+          <case>_<o>           each case of build_edges -- long, roll, both, n, lpac,
+                               window, equal, short -- under o = base, a2, one_anchor
+          lpac<l>_base         the lpac case on genomes of l = 200001, 200002, 200003
 """
 import gzip
 import json
@@ -298,8 +312,46 @@ def make_pairs():
                    "reads_without_region": int(none.sum()), "of_them_mapped": len(rescued)}, fh, indent=1)
 
 
+# ---- the reference's mem_matesw on the hand-built pairs ---------------------------------------
+def make_hand():
+    """every batch of tests/matesw_data.fixtures() through `ref_harness msw`: the lists afterwards and
+    the summed returns (SMMO), and in manifest.json what each batch was and a digest of what went in"""
+    import dataclasses
+    import hashlib
+    from tests import matesw_data as D
+    if not oracle.ref_available():
+        oracle.build(ref=True)
+    out = os.path.join(HERE, "msw", "hand")
+    os.makedirs(out, exist_ok=True)
+    man = {}
+    with tempfile.TemporaryDirectory() as d:
+        for name, (G, l_pac, case) in D.fixtures().items():
+            data = D.smmi_bytes(G, l_pac, case)
+            with open(os.path.join(d, "in.smmi"), "wb") as fh:
+                fh.write(data)
+            subprocess.run([REF, "msw", os.path.join(d, "in.smmi"), os.path.join(d, "out.smmo")], check=True)
+            with open(os.path.join(d, "out.smmo"), "rb") as fh:
+                res = fh.read()
+            regs, reg_off, n = D.smmo_parse(res)
+            gz_write(os.path.join(out, name + ".smmo.gz"), res)
+            builder = "build" if name.startswith("all_") else "build_fr" if name.startswith("fr_") else \
+                "build_edges:" + name.split("_")[0].rstrip("0123456789")
+            man[name] = {"builder": builder, "l_pac": int(l_pac), "pes": [[p.low, p.high, p.failed] for p in case.pes],
+                         "opt": dataclasses.asdict(case.opt), "pairs": len(case.pairs.group),
+                         "regions_in": int(sum(len(x) for x in case.pairs.lists)), "regions_out": int(regs.size),
+                         "n_sw": int(n.sum()), "input_sha256": hashlib.sha256(data).hexdigest()}
+            print(name, man[name]["pairs"], "pairs", regs.size, "regions", int(n.sum()), "SWs", flush=True)
+    with open(os.path.join(out, "manifest.json"), "w") as fh:
+        json.dump(man, fh, indent=1)
+
+
 if __name__ == "__main__":
+    if "--hand-only" in sys.argv:
+        make_hand()
+        sys.exit(0)
     if "--pairs-only" not in sys.argv:
         make_kswa()
     if "--kswa-only" not in sys.argv:
         make_pairs()
+    if "--kswa-only" not in sys.argv and "--pairs-only" not in sys.argv:
+        make_hand()

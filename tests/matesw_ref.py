@@ -5,7 +5,8 @@ Every SW is oracle.ksw_align2 (pinned to the reference's ksw_align2 at long
 targets by tests/test_ksw_align_long.py), every mem_sort_and_dedup is
 regfin_ref.sort_and_dedup (comparison-for-comparison ks_introsort).  The GPU
 stage (smem_matesw) is checked against matesw() list by list;
-tests/test_matesw.py pins matesw() to the reference's own SAM.
+tests/test_matesw.py pins matesw() to the reference's own mem_matesw on the
+hand-built lists (tests/golden/msw/hand) and to its SAM on the paired-end set.
 
 Regions are dicts of regfin_ref.FIELDS.  What the stage leaves to the host
 (SMEM_MSW_HOST: input lists copied through, n_sw = 0) is decided here the same
@@ -67,6 +68,9 @@ class Trace:
     dirs: list = field(default_factory=list)   # orientations an SW ran for
     byte: int = 0
     word: int = 0
+    host: str = ""         # why the pair is the host's: "mate", "window" or "list"
+    at: list = field(default_factory=list)        # (insertion index, list length before) per insertion
+    windows: list = field(default_factory=list)   # (orientation, rb, re) after the cuts, per open orientation
 
 
 def infer_dir(l_pac, b1, b2):
@@ -126,6 +130,7 @@ def matesw_one(opt, l_pac, fwd, pes, a, ms, ma, mat, tr):
             tr.clipped += 1
         rb = max(rb, 0)                                                       # :141
         re = min(re, l_pac << 1)                                              # :142
+        tr.windows.append((r, int(rb), int(re)))
         ref, ln = get_seq(l_pac, fwd, rb, re)                                 # :143
         if ln == re - rb:                                                     # :144
             if ln > MAX_TLEN:
@@ -157,6 +162,7 @@ def matesw_one(opt, l_pac, fwd, pes, a, ms, ma, mat, tr):
                     if x["score"] < b["score"]:
                         at = i
                         break
+                tr.at.append((at, len(ma)))
                 ma.insert(at, b)
                 tr.inserted += 1
             else:
@@ -180,6 +186,7 @@ def matesw_pair(opt, l_pac, fwd, pes, reads, lists, mat=None):
     tr = Trace()
     keep = [[dict(x) for x in lists[0]], [dict(x) for x in lists[1]]]
     if any(r.size < 1 or r.size > 256 for r in reads) or any(len(x) > MAX_REGS for x in lists):
+        tr.host = "mate" if any(r.size < 1 or r.size > 256 for r in reads) else "list"
         return keep, 0, MSW_HOST, tr
     a = [[dict(x) for x in lists[0]], [dict(x) for x in lists[1]]]
     b = [[dict(x) for x in a[i] if x["score"] >= a[i][0]["score"] - opt.pen_unpaired] for i in range(2)]   # :255-258
@@ -189,7 +196,8 @@ def matesw_pair(opt, l_pac, fwd, pes, reads, lists, mat=None):
             for j in range(min(len(b[i]), opt.max_matesw)):
                 k, a[1 - i] = matesw_one(opt, l_pac, fwd, pes, b[i][j], reads[1 - i], a[1 - i], mat, tr)
                 n += k
-    except ToHost:
+    except ToHost as e:
+        tr.host = str(e)
         return keep, 0, MSW_HOST, tr
     return a, n, 0, tr
 

@@ -2,7 +2,9 @@
 software/bwamem_pair.c:109-175, 252-263 that tests/test_matesw.py pins): both
 ends' lists, their offsets, n_sw and status equal, on the hand-built pairs of
 tests/matesw_data.py -- one group per branch, each group's size and what it
-reaches asserted -- and on the paired-end set of tests/golden/msw."""
+reaches asserted -- and on the paired-end set of tests/golden/msw.  On every batch
+of tests/golden/msw/hand the device's lists and n_sw are also compared with the
+reference's own mem_matesw (run_fixture)."""
 import os
 import subprocess
 import sys
@@ -46,6 +48,28 @@ def run_both(world, P, pes, opt, l_pac=D.L_PAC):
     return got, want, (codes, offs, regs, reg_off)
 
 
+def run_fixture(world, name):
+    """a batch of tests/golden/msw/hand on the GPU: equal to the restatement (whose result
+    tests/test_matesw.py computes, once), and to the reference's own lists and n where the pair stays
+    on the device; a pair left to the host comes back as it went in.  Returns (got, want, arrays, Case)."""
+    from tests import test_matesw as T
+    G, l_pac, case, arrays, ref, want = T.hand(name)
+    codes, offs, regs, reg_off = arrays
+    got = world["gpu"].matesw(D.pack(G), l_pac, codes, offs, regs, reg_off, c_pes(case.pes), c_opt(case.opt))
+    same(got, want)
+    out, off, n_sw, status, ms = got
+    r_regs, r_off, r_n = ref
+    for p in range(status.size):
+        mine = out[int(off[2 * p]):int(off[2 * p + 2])]
+        if status[p] == 0:
+            assert n_sw[p] == r_n[p] and np.array_equal(off[2 * p:2 * p + 3] - off[2 * p], r_off[2 * p:2 * p + 3] - r_off[2 * p])
+            assert mine.tobytes() == r_regs[int(r_off[2 * p]):int(r_off[2 * p + 2])].tobytes(), (name, p, case.pairs.group[p])
+        else:
+            assert status[p] == R.MSW_HOST and n_sw[p] == 0
+            assert mine.tobytes() == regs[int(reg_off[2 * p]):int(reg_off[2 * p + 2])].tobytes(), (name, p, case.pairs.group[p])
+    return got, want, arrays, case
+
+
 def same(got, want):
     out, off, n_sw, status, ms = got
     lists, w_sw, w_st, _ = want
@@ -65,6 +89,7 @@ def same(got, want):
 
 def test_matesw_every_orientation_open(world):
     P = world["all"]
+    run_fixture(world, "all_base")
     got, want, (codes, offs, regs, reg_off) = run_both(world, P, D.PES_ALL, R.Opt())
     same(got, want)
     out, off, n_sw, status, ms = got
@@ -103,6 +128,7 @@ def test_matesw_every_orientation_open(world):
 
 def test_matesw_only_fr_open(world):
     P = world["fr"]
+    run_fixture(world, "fr_base")
     got, want, (codes, offs, regs, reg_off) = run_both(world, P, D.PES_FR, R.Opt())
     same(got, want)
     out, off, n_sw, status, ms = got
@@ -130,6 +156,8 @@ def test_matesw_a2_scoring(world):
     tr = want[3]
     assert sum(t.word for t in tr) >= 300 and sum(t.inserted for t in tr) >= 100
     assert all(want[0][2 * p + 1][0]["score"] >= 200 for p in P.of("rescue_FR"))
+    for name in ["all_a2", "fr_a2"] + [f"{c}_a2" for c in D.EDGE_SIZES]:
+        run_fixture(world, name)
 
 
 def test_matesw_one_anchor_no_margin(world):
@@ -141,6 +169,9 @@ def test_matesw_one_anchor_no_margin(world):
         assert all(want[3][p].calls == calls for p in P.of("two_anchors"))
     got, want, _ = run_both(world, world["all"], D.PES_ALL, R.Opt(max_matesw=1, pen_unpaired=0))
     same(got, want)
+    for name in [f"{b}_{o}" for b in ("all", "fr") for o in ("one_anchor", "no_margin", "no_anchor")] + \
+            [f"{c}_one_anchor" for c in D.EDGE_SIZES]:
+        run_fixture(world, name)
 
 
 def test_matesw_window_past_the_limit(world):
@@ -152,6 +183,124 @@ def test_matesw_window_past_the_limit(world):
     host = [p for p in range(status.size) if status[p] == R.MSW_HOST]
     assert set(host) == set(range(status.size)) - set(P.of("empty"))
     assert not n_sw.any() and np.array_equal(off, reg_off) and out.tobytes() == regs.tobytes()
+
+
+@pytest.mark.parametrize("name", sorted(D.EDGE_SIZES))
+def test_matesw_edges(world, name):
+    """the groups of matesw_data.build_edges (tests/test_matesw.py asserts what each reaches)"""
+    got, want, (codes, offs, regs, reg_off), case = run_fixture(world, name + "_base")
+    out, off, n_sw, status, ms = got
+    P = case.pairs
+    host = {"long": P.of("long_1024_host") + P.of("two_1023_host"), "roll": list(range(status.size)),
+            "window": P.of("win_2049")}.get(name, [])
+    assert [p for p in range(status.size) if status[p]] == sorted(host)
+    if name == "roll":       # every pair rolled back after an insertion: the batch as it came
+        assert not n_sw.any() and np.array_equal(off, reg_off) and out.tobytes() == regs.tobytes()
+    if name == "both":
+        assert all(n_sw[p] == 2 and off[2 * p + 1] - off[2 * p] == 2 and off[2 * p + 2] - off[2 * p + 1] == 2
+                   for p in range(status.size))
+    if name == "long":
+        (p,) = P.of("long_1023")
+        assert off[2 * p + 2] - off[2 * p + 1] == R.MAX_REGS
+
+
+@pytest.mark.parametrize("l_pac", D.L_PAC_ODD)
+def test_matesw_l_pac_not_a_multiple_of_4(world, l_pac):
+    """the last .pac byte partly filled, and windows that end at, start at and pass l_pac"""
+    got, want, _, case = run_fixture(world, f"lpac{l_pac}_base")
+    assert l_pac % 4 and not got[3].any() and sum(t.inserted for t in want[3]) == 4
+
+
+def waves_per_cu():
+    import re
+    with open(os.path.join(ROOT, "bwa-mem-harp2_amd", "csrc", "matesw_kernels.h")) as fh:
+        m = re.search(r"MSW_WAVES_PER_CU\s*=\s*(\d+)", fh.read())
+    assert m, "csrc/matesw_kernels.h no longer spells MSW_WAVES_PER_CU = <n>: tell this test where the grid's size is"
+    return int(m.group(1))
+
+
+def test_matesw_more_pairs_than_the_grid(world):
+    """three rounds of the wave kernel's grid and a few pairs more: every block takes a second and a
+    third pair with what the one before left in LDS and scratch.  The kernel strides over the wave
+    list, which holds the pairs the pre-pass did not settle, so the kinds are laid out along that
+    list: 13 listed kinds of build_fr and build_edges in turn (a 129-region list, then an empty one;
+    a 256 bp word-mode mate, then one of 20 bp; an inserting pair, then one that stays below), a
+    period coprime to the grid's size, two of the 1000-region lists in place of two of them, and a
+    settled pair after every twelfth, so that the wave list is a strict subset of the batch.  With
+    the wave list in batch order no block meets the same kind twice (asserted); the atomic counter
+    that fills the list may reorder neighbours, and then about one successor in 13 is of the same
+    kind.  Equal to the restatement (computed once per distinct pair), and a second run byte for
+    byte: the wave list's order does not matter."""
+    import math
+    from smemgpu.lib import ALNREG_DT
+    from tests import test_matesw as T
+    slots = waves_per_cu() * world["gpu"].cu_count()
+    n_pairs = 3 * slots + 17
+    G, fr = world["G"], world["fr"]
+    opt = R.Opt(max_matesw=2)
+    edges = {n: T.hand(n + "_base")[2].pairs for n in D.EDGE_SIZES}
+
+    def pick(P, group, k=0):
+        p = P.of(group)[k]
+        return P.reads[2 * p], P.lists[2 * p], P.reads[2 * p + 1], P.lists[2 * p + 1]
+
+    kinds = [pick(edges["long"], "long_129"), pick(fr, "rescue_FR"), pick(edges["short"], "short_256"),
+             pick(edges["short"], "short_20"), pick(fr, "rescue_FR", 1), pick(edges["short"], "short_18"),
+             pick(edges["long"], "long_128"), pick(edges["both"], "both"), pick(edges["long"], "long_65"),
+             pick(fr, "two_anchors"), pick(edges["equal"], "equal", 1), pick(edges["n"], "n_5_FR"),
+             pick(fr, "second_anchor_skips")]
+    n_listed = len(kinds)
+    kinds += [pick(edges["long"], "long_1000"), pick(edges["long"], "long_1023"), pick(fr, "consistent")]
+    big, settled = (n_listed, n_listed + 1), n_listed + 2
+    assert math.gcd(n_listed, slots) == 1, "choose a number of listed kinds coprime to the grid's size"
+    order, i = [], 0
+    while len(order) < n_pairs:
+        order.append(big[0] if i == slots // 3 else big[1] if i == 2 * slots + 5 else i % n_listed)
+        i += 1
+        if i % 12 == 0 and len(order) < n_pairs:
+            order.append(settled)
+    order = np.array(order)
+
+    def regs_of(lst):
+        a = np.zeros(len(lst), dtype=ALNREG_DT)
+        for k, x in enumerate(lst):
+            for f in regfin_ref.FIELDS:
+                a[k][f] = x[f]
+        return a
+
+    one, res = [], []
+    for r0, l0, r1, l1 in kinds:             # each kind: its arrays, and the restatement of it alone
+        P = D.Pairs()
+        P.add("x", r0, l0, r1, l1)
+        lists, n, st, tr = R.matesw(opt, D.L_PAC, G, D.PES_FR, *P.arrays())
+        assert st[0] == 0
+        one.append((r0, r1, regs_of(l0), regs_of(l1)))
+        res.append((regs_of(lists[0]), regs_of(lists[1]), n[0], n[0] > 0 or lists[0] != l0 or lists[1] != l1, tr[0].calls))
+    reads = [x for k in order for x in one[k][:2]]
+    rl = [x for k in order for x in one[k][2:]]
+    codes = np.concatenate(reads)
+    offs = np.concatenate([[0], np.cumsum([x.size for x in reads])]).astype(np.uint64)
+    regs = np.concatenate(rl)
+    reg_off = np.concatenate([[0], np.cumsum([x.size for x in rl])]).astype(np.uint64)
+    wl = [x for k in order for x in res[k][:2]]
+    w_regs = np.concatenate(wl)
+    w_off = np.concatenate([[0], np.cumsum([x.size for x in wl])]).astype(np.uint64)
+    w_sw = np.array([res[k][2] for k in order], dtype=np.int32)
+    # the test's own preconditions: the kinds meant for the wave list are listed (an anchor gets past the skip
+    # test) and do something, the settled one is not; more than two rounds of the grid do something; and along
+    # the wave list in batch order a block's next pair, `slots` entries on, is never of the kind it just ran
+    assert all(res[k][4] > 0 and res[k][3] for k in range(settled)) and res[settled][4] == 0 and not res[settled][3]
+    wave = order[order != settled]
+    assert wave.size > 2 * slots and 0 < n_pairs - wave.size
+    assert (wave[:-slots] != wave[slots:]).all() and (wave[:-2 * slots] != wave[2 * slots:]).all()
+    args = (world["pac"], D.L_PAC, codes, offs, regs, reg_off, c_pes(D.PES_FR), c_opt(opt))
+    out, off, n_sw, status, ms = world["gpu"].matesw(*args)
+    assert not status.any() and np.array_equal(n_sw, w_sw)
+    assert np.array_equal(off, w_off)
+    bad = np.nonzero(out != w_regs)[0]
+    assert bad.size == 0, (int(bad[0]), out[bad[0]], w_regs[bad[0]])
+    again = world["gpu"].matesw(*args)
+    assert again[0].tobytes() == out.tobytes() and np.array_equal(again[1], off) and np.array_equal(again[2], n_sw)
 
 
 def test_matesw_golden_pairs(world):
@@ -183,6 +332,22 @@ def test_matesw_contract(world):
     assert again[0].tobytes() == full[0].tobytes() and np.array_equal(again[1], full[1])
     grown = gpu.matesw(pac, D.L_PAC, codes, offs, regs, reg_off, pes, opt, regs_cap=1)
     assert grown[0].tobytes() == full[0].tobytes()
+    # a batch of which some pairs are the host's (copied through) and others grow
+    from tests import test_matesw as T
+    case = T.hand("window_base")[2]
+    w_args = (pac, D.L_PAC) + case.pairs.arrays() + (c_pes(case.pes), c_opt(case.opt))
+    w_full = gpu.matesw(*w_args)
+    lens_in, lens_out = np.diff(w_args[5].astype(np.int64)), np.diff(w_full[1].astype(np.int64))
+    assert 0 < int(w_full[3].sum()) < w_full[3].size and (lens_out > lens_in).any()
+    assert all((lens_out[2 * p:2 * p + 2] == lens_in[2 * p:2 * p + 2]).all() for p in np.nonzero(w_full[3])[0])
+    w_need = int(w_full[1][-1])
+    with pytest.raises(smemgpu.SmemError) as e:
+        gpu.matesw(*w_args, regs_cap=w_need - 1, grow=False)
+    assert e.value.n_regs == w_need
+    for cap in (dict(regs_cap=w_need, grow=False), dict(regs_cap=1)):
+        w_again = gpu.matesw(*w_args, **cap)
+        assert w_again[0].tobytes() == w_full[0].tobytes() and np.array_equal(w_again[1], w_full[1])
+        assert np.array_equal(w_again[3], w_full[3])
     # no pairs
     e0 = gpu.matesw(pac, D.L_PAC, np.zeros(0, np.uint8), np.zeros(1, np.uint64), regs[:0], np.zeros(1, np.uint64), pes, opt)
     assert e0[0].size == 0 and e0[1].tolist() == [0] and e0[2].size == 0
