@@ -350,8 +350,13 @@ struct smem_gpu {
     int kt_k = 0;
     int kt_d = 0;                   // the table's facts (kmer_facts): see SeedParams::kt_d, kt_min
     uint64_t kt_min[16] = {0};
-    uint64_t kt_min_next = 0;       // the smallest size of level kt_k + 1, which is reduced but not stored (0: a
+    uint64_t kt_min_next = 0;       // the smallest size of level kt_k + 1, which is reduced but not reported (0: a
                                     // string is absent, or the level was not reduced: kt_k = 15)
+    // the leaf: level kt_k + 1 stored behind the kt_k reported ones, in the same allocation (its smallest
+    // size is kt_min_next).  kt_leaf_strict: no present string of the leaf has a one-base extension of its
+    // own size; kt_leaf_next: the smallest size of level kt_k + 2, reduced from the leaf and not stored
+    bool kt_leaf = false, kt_leaf_strict = false;
+    uint64_t kt_leaf_next = 0;
     double kt_build_s = 0.0;        // seconds the table's build and reduction took
     uint64_t* d_sa = nullptr;       // sampled SA (smem_gpu_load_sa), n_sa + 1 words
     uint8_t* d_pac = nullptr;       // 2-bit forward strand (smem_gpu_load_pac)
@@ -899,7 +904,7 @@ static smem_gpu_t* gpu_handle(int device, uint64_t bwt_size, uint64_t primary, c
     return g;
 }
 
-static int kmer_table_build(smem_gpu_t* g, int k, const char* who);
+static int kmer_table_build(smem_gpu_t* g, int k, bool leaf, const char* who);
 
 // the index resident on g's device: upload, Occ64 re-layout, the k-mer table
 // (the index pointers stay null on failure)
@@ -958,13 +963,24 @@ static int gpu_open(smem_gpu_t* g, const uint32_t* bwt) {
     // ALLOCATED is not an error: the kernel then runs every call on the plain path.  Any other failure
     // (a device error while building) fails the handle like the Occ64 layout's does
     int kk = kKmerDefault;
-    // (the handle's own table is at most kKmerDefault deep: 13 would be 1.4 GB, 15 23 GB;
+    // (the handle's own table reports at most kKmerDefault levels: 15 would be 23 GB;
     // smem_gpu_set_kmer_table takes a deeper one from a caller who means it)
     if (const char* v = getenv("SMEM_GPU_KMER_K")) kk = std::max(0, std::min(kKmerDefault, atoi(v)));
     // (no deeper than the index has strings for: 4^k <= its length)
     while (kk > 1 && (1ull << (2 * kk)) > g->L2[4]) --kk;
+    // behind the default's levels one leaf level, kKmerDefault + 1 (1.07 GB more), where the index has
+    // strings for it too: a launch probes it when it is complete and strict (smem_kmer_leaf_probe_depth).
+    // SMEM_GPU_KMER_LEAF=0: none, for A/B.  A small index gets none: its table is what it was
+    bool leaf = kk == kKmerDefault && (1ull << (2 * (kKmerDefault + 1))) <= g->L2[4];
+    if (const char* v = getenv("SMEM_GPU_KMER_LEAF")) leaf = leaf && atoi(v) != 0;
     if (kk > 0) {
-        const int rc = kmer_table_build(g, kk, "smem_gpu_init: k-mer table");
+        int rc = kmer_table_build(g, kk, leaf, "smem_gpu_init: k-mer table");
+        if (rc == SMEM_E_NOMEM && leaf) {
+            fprintf(stderr, "[smem_gpu] no memory for the k-mer table's leaf level %d: depth %d without it\n", kk + 1, kk);
+            (void)hipGetLastError();
+            g_err[0] = 0;
+            rc = kmer_table_build(g, kk, false, "smem_gpu_init: k-mer table");
+        }
         if (rc == SMEM_E_NOMEM) {
             fprintf(stderr, "[smem_gpu] no memory for the k-mer table of depth %d: seeding runs the plain kernel\n", kk);
             (void)hipGetLastError();
@@ -1094,32 +1110,59 @@ int smem_kmer_probe_depth(const uint64_t* mn, int k, uint64_t min_next, int64_t 
     return smem_kmer_call_depth(mn, D, min_intv);
 }
 
-// the table of 1..k bases and its facts on g's device (g->mu held, no batch running); k = 0 frees it
-static int kmer_table_build(smem_gpu_t* g, int k, const char* who) {
+// the same on a table that stores one level more than the k it reports: the leaf, level k + 1, whose
+// smallest size is min_next.  The leaf may be probed for min_intv when levels 1 .. k + 1 are complete,
+// min_next >= min_intv, and the leaf is strict (leaf_strict: no present string of k + 1 bases has a one-base
+// extension of its own size) or level k + 2 is complete (its minimum leaf_next; 0 or ~0: not), which
+// implies strictness.  Level k + 2's completeness is used for nothing else (DESIGN.md §5 "A leaf level").
+// Otherwise, and without a leaf, this is smem_kmer_probe_depth(mn, k, min_next, min_intv).
+// (only mn[1 .. k] is read: k = 14 gives at most 15, k = 15 has no level 16 to probe)
+int smem_kmer_leaf_probe_depth(const uint64_t* mn, int k, uint64_t min_next, int leaf, int leaf_strict,
+                               uint64_t leaf_next, int64_t min_intv) {
+    if (min_intv < 1) min_intv = 1;
+    bool ok = leaf && k >= 1 && k <= 14 && min_next != ~0ull && min_next >= (uint64_t)min_intv;
+    for (int l = 1; ok && l <= k; ++l) ok = mn[l] > 0;
+    ok = ok && (leaf_strict || (leaf_next > 0 && leaf_next != ~0ull));
+    return ok ? k + 1 : smem_kmer_probe_depth(mn, k, min_next, min_intv);
+}
+
+// the depth g's launches probe at for min_intv
+static int kmer_launch_depth(const smem_gpu_t* g, int64_t min_intv) {
+    return smem_kmer_leaf_probe_depth(g->kt_min, g->kt_k, g->kt_min_next, g->kt_leaf, g->kt_leaf_strict,
+                                      g->kt_leaf_next, min_intv);
+}
+
+// the table of 1..k bases (leaf: and behind them level k + 1, k <= 13) and its facts on g's device (g->mu
+// held, no batch running); k = 0 frees it
+static int kmer_table_build(smem_gpu_t* g, int k, bool leaf, const char* who) {
     if (g->d_kt) {
         HIP_TRY(hipDeviceSynchronize());  // no batch may still read it
         (void)hipFree(g->d_kt);
         g->d_kt = nullptr;
         g->kt_k = g->kt_d = 0;
-        g->kt_min_next = 0;
+        g->kt_min_next = g->kt_leaf_next = 0;
+        g->kt_leaf = g->kt_leaf_strict = false;
         std::memset(g->kt_min, 0, sizeof(g->kt_min));
     }
     if (k == 0) return SMEM_OK;
     const double t0 = now_s();
-    const uint64_t n = ((1ull << (2 * (k + 1))) - 4) / 3;  // levels 1..k
+    const int ks = k + (leaf ? 1 : 0);                      // the stored levels
+    const uint64_t n = ((1ull << (2 * (ks + 1))) - 4) / 3;  // levels 1..ks
     uint4* p = nullptr;
     unsigned long long* d_mn = nullptr;
     hipError_t e = hipMalloc(&p, n * sizeof(uint4));
     if (e != hipSuccess) return fail(SMEM_E_NOMEM, who, e);
     e = hipMalloc(&d_mn, 16 * sizeof(unsigned long long));
     unsigned long long mn[16] = {0};
-    if (e == hipSuccess) e = smem_launch_kmer_table(g->d_occ64, g->primary, g->L2, k, p, nullptr);
-    if (e == hipSuccess) e = smem_launch_kmer_min(p, k, d_mn, nullptr);
-    // level k + 1 is reduced from level k without being stored (mn[k + 1]; k = 15: no room, not reduced)
-    const bool next = k <= 14;
-    if (e == hipSuccess && next) e = smem_launch_kmer_min_next(g->d_occ64, g->primary, g->L2, p, k, d_mn + k + 1, nullptr);
+    if (e == hipSuccess) e = smem_launch_kmer_table(g->d_occ64, g->primary, g->L2, ks, p, nullptr);
+    if (e == hipSuccess) e = smem_launch_kmer_min(p, ks, d_mn, nullptr);
+    // level ks + 1 is reduced from level ks without being stored (mn[ks + 1]; ks = 15: no room, not reduced),
+    // and with it whether level ks is strict (mn[0], which no level uses: 1 if it is not)
+    const bool next = ks <= 14;
+    if (e == hipSuccess && next)
+        e = smem_launch_kmer_min_next(g->d_occ64, g->primary, g->L2, p, ks, d_mn + ks + 1, d_mn, nullptr);
     if (e == hipSuccess)
-        e = hipMemcpy(mn, d_mn, sizeof(unsigned long long) * (size_t)(k + 1 + next), hipMemcpyDeviceToHost);
+        e = hipMemcpy(mn, d_mn, sizeof(unsigned long long) * (size_t)(ks + 1 + next), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (d_mn) (void)hipFree(d_mn);
     if (e != hipSuccess) {
@@ -1129,16 +1172,24 @@ static int kmer_table_build(smem_gpu_t* g, int k, const char* who) {
     g->d_kt = p;
     g->kt_k = k;
     for (int l = 1; l <= k; ++l) g->kt_min[l] = mn[l];
-    g->kt_min_next = next ? mn[k + 1] : 0;
+    g->kt_min_next = leaf || next ? mn[k + 1] : 0;
+    g->kt_leaf = leaf;
+    g->kt_leaf_strict = leaf && next && mn[0] == 0;
+    g->kt_leaf_next = leaf && next ? mn[ks + 1] : 0;
     g->kt_d = smem_kmer_depth(g->kt_min, k);
     g->kt_build_s = now_s() - t0;
-    if (getenv("SMEM_GPU_TIMES"))
+    if (getenv("SMEM_GPU_TIMES")) {
+        char lf[128] = "no leaf";
+        if (leaf)
+            snprintf(lf, sizeof lf, "leaf level %d stored, %sstrict, level %d min %llu", k + 1,
+                     g->kt_leaf_strict ? "" : "not ", k + 2, (unsigned long long)g->kt_leaf_next);
         fprintf(stderr,
-                "[smem_gpu] k-mer table: k %d, %.1f MB, D %d, minsz[D] %llu, minsz[k] %llu, unstored level %d min %llu, "
+                "[smem_gpu] k-mer table: k %d, %.1f MB, D %d, minsz[D] %llu, minsz[k] %llu, %s level %d min %llu, %s, "
                 "probe depth %d (min_intv 1), built in %.3f s\n",
                 k, n * 16.0 / 1e6, g->kt_d, (unsigned long long)g->kt_min[g->kt_d], (unsigned long long)g->kt_min[k],
-                k + 1, (unsigned long long)g->kt_min_next, smem_kmer_probe_depth(g->kt_min, k, g->kt_min_next, 1),
+                leaf ? "leaf" : "unstored", k + 1, (unsigned long long)g->kt_min_next, lf, kmer_launch_depth(g, 1),
                 g->kt_build_s);
+    }
     return SMEM_OK;
 }
 
@@ -1149,7 +1200,30 @@ int smem_gpu_set_kmer_table(smem_gpu_t* g, int k) {
     if (int r = gpu_check(g)) return r;
     std::lock_guard<std::mutex> lk(g->mu);
     HIP_TRY(hipSetDevice(g->device));
-    return kmer_table_build(g, k, "smem_gpu_set_kmer_table");
+    return kmer_table_build(g, k, false, "smem_gpu_set_kmer_table");
+}
+
+int smem_gpu_set_kmer_table_leaf(smem_gpu_t* g, int k) {
+    g_err[0] = 0;
+    if (!g || k < 1 || k > 13) return fail(SMEM_E_ARG, "smem_gpu_set_kmer_table_leaf: k must be 1..13");
+    gpu_wait(g);
+    if (int r = gpu_check(g)) return r;
+    std::lock_guard<std::mutex> lk(g->mu);
+    HIP_TRY(hipSetDevice(g->device));
+    bool leaf = true;
+    if (const char* v = getenv("SMEM_GPU_KMER_LEAF")) leaf = atoi(v) != 0;
+    return kmer_table_build(g, k, leaf, "smem_gpu_set_kmer_table_leaf");
+}
+
+int smem_gpu_kmer_leaf_facts(smem_gpu_t* g, int* level, uint64_t* leaf_min, int* strict, uint64_t* next_min) {
+    if (!g) return SMEM_E_ARG;
+    gpu_wait(g);
+    const bool leaf = g->d_kt && g->kt_leaf;
+    if (level) *level = leaf ? g->kt_k + 1 : 0;
+    if (leaf_min) *leaf_min = leaf ? g->kt_min_next : 0;
+    if (strict) *strict = leaf && g->kt_leaf_strict;
+    if (next_min) *next_min = leaf ? g->kt_leaf_next : 0;
+    return SMEM_OK;
 }
 
 int smem_gpu_kmer_facts(smem_gpu_t* g, int* k, int* depth, uint64_t* minsz, int n_minsz) {
@@ -1165,7 +1239,7 @@ int smem_gpu_kmer_probe_depth(smem_gpu_t* g, int64_t min_intv, uint64_t* min_nex
     if (!g) return SMEM_E_ARG;
     gpu_wait(g);
     if (min_next) *min_next = g->kt_min_next;
-    return g->d_kt ? smem_kmer_probe_depth(g->kt_min, g->kt_k, g->kt_min_next, min_intv) : 0;
+    return g->d_kt ? kmer_launch_depth(g, min_intv) : 0;
 }
 
 int smem_gpu_set_intv_cap(smem_gpu_t* g, int cap_per_read) {
@@ -1381,7 +1455,7 @@ static void fill_params(smem_batch_t* b, const smem_opt_t* o, smem::SeedParams& 
     P.occ64 = b->g->d_occ64;
     P.occ192 = b->g->d_occ192;
     P.kt = b->g->d_kt;
-    P.kt_k = b->g->kt_k;
+    P.kt_k = b->g->kt_k + (b->g->kt_leaf ? 1 : 0);  // the stored levels: kt_slot reaches the leaf
     P.primary = b->g->primary;
     std::memcpy(P.L2, b->g->L2, sizeof(P.L2));
     P.codes = b->d_codes.p;
@@ -1393,10 +1467,10 @@ static void fill_params(smem_batch_t* b, const smem_opt_t* o, smem::SeedParams& 
     P.start_width = o->start_width;
     // the depth below which the default kernel keeps a call's entries virtual: a re-seeding call's min_intv
     // is its match's size + 1, at most split_width + 1 (software/bwamem.c:272-276)
-    // (smem_kmer_probe_depth: up to the table's deepest level where the unstored level after it is complete)
-    P.kt_dp0 = smem_kmer_probe_depth(b->g->kt_min, b->g->kt_k, b->g->kt_min_next, o->start_width);
-    P.kt_dp1 = smem_kmer_probe_depth(b->g->kt_min, b->g->kt_k, b->g->kt_min_next,
-                                     (int64_t)std::max(o->split_width, 0) + 1);
+    // (smem_kmer_leaf_probe_depth: up to the table's deepest level where the unstored level after it is
+    // complete, or the leaf where that one is complete and strict)
+    P.kt_dp0 = kmer_launch_depth(b->g, o->start_width);
+    P.kt_dp1 = kmer_launch_depth(b->g, (int64_t)std::max(o->split_width, 0) + 1);
     P.scratch = b->d_scratch.p;
     P.cap_list = b->cap_list;
     const char* dbg = getenv("SMEM_DEBUG_FLAGS");
@@ -4468,7 +4542,7 @@ int smem_gpu_memory(smem_gpu_t* g, uint64_t* index_bytes, uint64_t* batch_bytes,
     ix += (n_ref * 16 + 16) * sizeof(uint32_t);                                   // Occ64
     if (g->d_bwt) ix += (g->bwt_size + 16) * sizeof(uint32_t);                    // reference layout (A/B builds)
     if (g->d_occ192) ix += ((2 * n_ref + 2) / 3 * 16 + 16) * sizeof(uint32_t);
-    if (g->d_kt) ix += (((1ull << (2 * (g->kt_k + 1))) - 4) / 3) * 16;
+    if (g->d_kt) ix += (((1ull << (2 * (g->kt_k + (g->kt_leaf ? 1 : 0) + 1))) - 4) / 3) * 16;  // the leaf included
     if (g->d_sa) ix += (g->n_sa + 1) * sizeof(uint64_t);                          // densified SA
     if (g->d_sa_raw) ix += ((g->L2[4] >> 5) + 2) * sizeof(uint64_t);              // the uploaded .sa (sa_intv 32)
     if (g->d_pac) ix += (uint64_t)(g->l_pac + 3) / 4 + 64;

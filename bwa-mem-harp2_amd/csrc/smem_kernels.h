@@ -49,7 +49,7 @@ struct SeedParams {
     uint64_t* dbg_buf;         // stamped diagnostic variant: 8 x u64 per wave
     uint64_t* tspan;           // [0] max of ~(wave start), [1] max of wave end (s_memrealtime), nullptr: none
     const uint4* kt;           // k-mer bi-interval table (smem_launch_kmer_table; variant 23), nullptr: none
-    int kt_k;                  // its longest k-mer
+    int kt_k;                  // its longest k-mer: every level the table stores, a leaf level included
     int kt_dp0, kt_dp1;        // seed_wp_kernel SKIP: the probe depth of calls with min_intv = start_width and of
                                // re-seeding calls (min_intv <= split_width + 1): smem_kmer_probe_depth, <= kt_k; 0: none
 };
@@ -105,9 +105,10 @@ hipError_t smem_launch_kmer_table(const uint32_t* occ64, uint64_t primary, const
 // mn[L] = the smallest x2 of table level L, L = 1..k (mn: k + 1 device words)
 hipError_t smem_launch_kmer_min(const uint4* kt, int k, unsigned long long* mn, hipStream_t st);
 // *mn_next = the smallest size among the strings of k + 1 bases (0: one is absent), computed from level k
-// and the index without storing the level (k <= 14; one device word)
+// and the index without storing the level (k <= 14; one device word).  *not_strict (may be null; one device
+// word) = 1 if a present string of k bases has a one-base extension as large as itself, else 0
 hipError_t smem_launch_kmer_min_next(const uint32_t* occ64, uint64_t primary, const uint64_t* L2, const uint4* kt, int k,
-                                     unsigned long long* mn_next, hipStream_t st);
+                                     unsigned long long* mn_next, unsigned long long* not_strict, hipStream_t st);
 hipError_t smem_launch_finalize(const smem::FinalizeParams* F, int write, hipStream_t st);
 hipError_t smem_launch_fill_i32(int32_t* p, int32_t v, int n, hipStream_t st);
 hipError_t smem_launch_pack_intv(const smem::Intv* in, uint64_t n, uint4* out, hipStream_t st);

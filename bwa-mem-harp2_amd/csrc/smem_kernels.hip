@@ -1563,13 +1563,18 @@ __global__ __launch_bounds__(256) void kmer_level_min_kernel(const uint4* __rest
 
 // the same for level L + 1, which the table does not store: each thread extends the L-mers W of a strided
 // share backward by each base (as kmer_table_kernel does for a stored level; an absent W contributes 0)
-// and keeps the smallest size, nothing is written but the wave's one atomic into *mn_next (preset to ~0)
+// and keeps the smallest size, nothing is written but the wave's one atomic into *mn_next (preset to ~0).
+// The same four sizes tell whether level L is strict: a present W with an extension of its own size (the
+// other three absent, W not at the text's start) sets *not_strict (preset to 0; null: not asked for).  The
+// index holds both strands, so the backward extensions of every W are the forward ones of every rc(W)
 __global__ __launch_bounds__(256) void kmer_next_level_min_kernel(SeedParams P, const uint4* __restrict__ kt, int L,
-                                                                  unsigned long long* __restrict__ mn_next) {
+                                                                  unsigned long long* __restrict__ mn_next,
+                                                                  unsigned long long* __restrict__ not_strict) {
     const uint64_t n = 1ull << (2 * L);
     const uint4* lev = kt + (n - 4) / 3;
     const uint4* o = reinterpret_cast<const uint4*>(P.occ64);  // block b: o[2b] counts, o[2b + 1] symbols
     unsigned long long m = ~0ull;
+    bool eq = false;
     for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += (uint64_t)gridDim.x * blockDim.x) {
         const uint4 e = lev[w];
         const uint64_t a = p_x0(e), b = p_x1(e), s = p_x2(e);
@@ -1586,6 +1591,7 @@ __global__ __launch_bounds__(256) void kmer_next_level_min_kernel(SeedParams P, 
             uint64_t na, nb, ns;
             extend_counts64<false>(P, a, b, s, c, kk, ll, vk, vl, na, nb, ns);
             m = ns < m ? ns : m;
+            eq |= ns == s;
         }
     }
 #pragma unroll
@@ -1594,6 +1600,7 @@ __global__ __launch_bounds__(256) void kmer_next_level_min_kernel(SeedParams P, 
         m = t < m ? t : m;
     }
     if ((threadIdx.x & 63) == 0) atomicMin(mn_next, m);
+    if (not_strict && __any(eq) && (threadIdx.x & 63) == 0) atomicMax(not_strict, 1ull);
 }
 
 // Occ64 -> Occ192 (see rank192); one thread per 64-B line of 192 symbols
@@ -1662,7 +1669,8 @@ extern "C" hipError_t smem_launch_kmer_min(const uint4* kt, int k, unsigned long
 }
 
 extern "C" hipError_t smem_launch_kmer_min_next(const uint32_t* occ64, uint64_t primary, const uint64_t* L2, const uint4* kt,
-                                                 int k, unsigned long long* mn_next, hipStream_t st) {
+                                                 int k, unsigned long long* mn_next, unsigned long long* not_strict,
+                                                 hipStream_t st) {
     if (k < 1 || k > 14) return hipErrorInvalidValue;
     smem::SeedParams P;
     memset(&P, 0, sizeof(P));
@@ -1670,10 +1678,11 @@ extern "C" hipError_t smem_launch_kmer_min_next(const uint32_t* occ64, uint64_t 
     P.primary = primary;
     for (int c = 0; c < 5; ++c) P.L2[c] = L2[c];
     hipError_t e = hipMemsetAsync(mn_next, 0xFF, sizeof(unsigned long long), st);
+    if (e == hipSuccess && not_strict) e = hipMemsetAsync(not_strict, 0, sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
     const uint64_t n = 1ull << (2 * k);
     const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 16384);
-    hipLaunchKernelGGL(smem::kmer_next_level_min_kernel, dim3(grid), dim3(256), 0, st, P, kt, k, mn_next);
+    hipLaunchKernelGGL(smem::kmer_next_level_min_kernel, dim3(grid), dim3(256), 0, st, P, kt, k, mn_next, not_strict);
     return hipGetLastError();
 }
 

@@ -28,6 +28,7 @@ EXPORTED = [
     "smem_gpu_set_lanes_per_cu", "smem_gpu_set_intv_cap", "smem_gpu_set_kernel_variant", "smem_gpu_get_kernel_variant", "smem_gpu_grid_reads", "smem_gpu_set_kmer_table", "smem_batch_debug", "smem_strerror",
     "smem_gpu_kmer_facts", "smem_gpu_seed_kernel", "smem_kmer_depth", "smem_kmer_call_depth",
     "smem_kmer_probe_depth", "smem_gpu_kmer_probe_depth",
+    "smem_gpu_set_kmer_table_leaf", "smem_kmer_leaf_probe_depth", "smem_gpu_kmer_leaf_facts",
     "smem_gpu_build_id",
     "smem_bwt_build_sa", "smem_bwt_build_gpu_sa", "smem_sa_read", "smem_sa_write", "smem_sa_free", "smem_gpu_load_sa",
     "smem_batch_sa", "smem_batch_sa_results",
@@ -385,6 +386,14 @@ def load() -> C.CDLL:
         lib.smem_kmer_probe_depth.restype = C.c_int
         lib.smem_gpu_kmer_probe_depth.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_uint64)]
         lib.smem_gpu_kmer_probe_depth.restype = C.c_int
+    if hasattr(lib, "smem_kmer_leaf_probe_depth"):  # absent from A/B libraries built before the leaf level
+        lib.smem_gpu_set_kmer_table_leaf.argtypes = [C.c_void_p, C.c_int]
+        lib.smem_gpu_set_kmer_table_leaf.restype = C.c_int
+        lib.smem_kmer_leaf_probe_depth.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_int64]
+        lib.smem_kmer_leaf_probe_depth.restype = C.c_int
+        lib.smem_gpu_kmer_leaf_facts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_uint64)]
+        lib.smem_gpu_kmer_leaf_facts.restype = C.c_int
     if hasattr(lib, "smem_batch_debug"):  # absent from older A/B builds
         lib.smem_batch_debug.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     lib.smem_strerror.argtypes = [C.c_int]
@@ -718,6 +727,21 @@ class Gpu:
         """Build (k = 1..15) or free (0) the device k-mer bi-interval table."""
         _check(load().smem_gpu_set_kmer_table(self._h, k), "smem_gpu_set_kmer_table")
 
+    def set_kmer_table_leaf(self, k: int) -> None:
+        """Build the table of k levels (1..13) with level k + 1 stored behind them as its leaf
+        (smem_gpu_set_kmer_table_leaf; SMEM_GPU_KMER_LEAF=0 in the environment: without the leaf)."""
+        _check(load().smem_gpu_set_kmer_table_leaf(self._h, k), "smem_gpu_set_kmer_table_leaf")
+
+    def kmer_leaf_facts(self) -> dict:
+        """The table's leaf (smem_gpu_kmer_leaf_facts): its level k + 1 (0: none), its smallest size, whether
+        it is strict (no present string of it has a one-base extension of its own size), and the smallest
+        size of level k + 2, which the build reduced from it."""
+        lv, st = C.c_int(0), C.c_int(0)
+        mn, nx = C.c_uint64(0), C.c_uint64(0)
+        _check(load().smem_gpu_kmer_leaf_facts(self._h, C.byref(lv), C.byref(mn), C.byref(st), C.byref(nx)),
+               "smem_gpu_kmer_leaf_facts")
+        return {"level": lv.value, "min": int(mn.value), "strict": bool(st.value), "next_min": int(nx.value)}
+
     def kmer_facts(self) -> dict:
         """The k-mer table's facts (smem_gpu_kmer_facts): k its depth (0: none), D the largest level
         below k such that every string of D + 1 bases occurs, minsz[L] the smallest interval size of
@@ -731,7 +755,8 @@ class Gpu:
         """The depth a launch probes the table at for calls with this min_intv, and the smallest size of
         the unstored level k + 1 (smem_gpu_kmer_probe_depth).  kmer_facts()["D"] counts the stored levels
         only (D <= k - 1); the kernel may also rely on level k + 1, which the build reduced without
-        storing it, so the depth here is k where kmer_facts would say k - 1.  A run takes it for
+        storing it, so the depth here is k where kmer_facts would say k - 1, and k + 1 where the table has
+        a leaf that vouches for itself (kmer_leaf_facts; min_next is then the leaf's minimum).  A run takes it for
         min_intv = start_width (a read's first calls) and split_width + 1 (its re-seeding calls)."""
         nx = C.c_uint64(0)
         dp = load().smem_gpu_kmer_probe_depth(self._h, int(min_intv), C.byref(nx))

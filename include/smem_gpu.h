@@ -818,7 +818,7 @@ int  smem_gpu_set_kernel_variant(smem_gpu_t *gpu, int variant);
  * Mind the collision: the number this getter reports for a default handle (49)
  * is also the plain kernel's, and bench.py / tools/traffic.py key the recorded
  * counters (profiles/traffic*.json) by it.  The committed records hold kernel
- * 68's counters at table depth 12 under "variant": 49, so the roofline and
+ * 68's counters at its default depth under "variant": 49, so the roofline and
  * counter fields bench.py prints for a `--variant 49` run, or for a run with
  * another SMEM_GPU_KMER_K, are those records', not that run's.
  * A/B (make AB=1): 69, 70 = 68 with 32 reads / 12 entries, 28 / 14; 40 32 reads / 20 entries / 3 blocks; 41 32 / 16; 42 24 / 24; 43 = 40
@@ -835,14 +835,15 @@ int  smem_gpu_seed_kernel(smem_gpu_t *gpu);
 int  smem_gpu_set_kmer_table(smem_gpu_t *gpu, int k);
 /* A handle builds this table for itself when the index is loaded (k = 12, or
  * SMEM_GPU_KMER_K from the environment; no deeper than 4^k <= the index's
- * length; k = 0 or a failed allocation: no table, the plain path), and
+ * length; at 12 levels with a leaf level behind them, below; k = 0 or a
+ * failed allocation: no table, the plain path), and
  * smem_gpu_set_kmer_table replaces or removes it.  The table's facts: *k its
  * depth (0: none), minsz[L] the smallest interval size among the strings of L
  * bases (0: one is absent; L = 1..k, n_minsz words written), *depth the
  * largest level D < k such that every string of D + 1 bases occurs.  A
  * bwt_smem1 call skips the extends of strings of fewer than
- * smem_kmer_probe_depth(minsz, k, min_next, min_intv) bases (below: D, or k
- * where the unstored level k + 1 is complete too), min_intv taken as
+ * smem_kmer_leaf_probe_depth(...) bases (below: D, or k where the unstored
+ * level k + 1 is complete too, or k + 1 where a leaf vouches for itself), min_intv taken as
  * start_width for a read's first calls and as split_width + 1 (the most a
  * re-seeding call can ask for) for its re-seeding calls. */
 int  smem_gpu_kmer_facts(smem_gpu_t *gpu, int *k, int *depth, uint64_t *minsz, int n_minsz);
@@ -868,6 +869,30 @@ int  smem_kmer_call_depth(const uint64_t *mn, int depth, int64_t min_intv);
  * split_width + 1. */
 int  smem_kmer_probe_depth(const uint64_t *mn, int k, uint64_t min_next, int64_t min_intv);
 int  smem_gpu_kmer_probe_depth(smem_gpu_t *gpu, int64_t min_intv, uint64_t *min_next);
+/* The leaf.  Behind the k levels it reports a table may store one more, level
+ * k + 1, in the same allocation (16 B x 4^(k+1) more; at k = 12: 1.07 GB, the
+ * table 1.43 GB).  smem_gpu_init builds it when the table has the default's 12
+ * levels and 4^13 <= the index's length (SMEM_GPU_KMER_LEAF=0: never; if the
+ * larger allocation fails, the 12 levels alone are tried before the plain
+ * kernel); smem_gpu_set_kmer_table_leaf builds k levels (1..13) and a leaf on
+ * any index; smem_gpu_set_kmer_table builds exactly k levels and no leaf.
+ * smem_gpu_kmer_facts reports the same k, D and minsz with or without a leaf,
+ * and *min_next above is then the leaf's own minimum.  While the leaf is built
+ * the four one-base extensions of each of its strings are formed once: their
+ * minimum is level k + 2's (next_min; 0: a string is absent), and *strict
+ * tells that no present string of k + 1 bases has an extension of its own
+ * size.  smem_kmer_leaf_probe_depth is the depth a launch takes: k + 1 when
+ * levels 1 .. k + 1 are complete, min_next >= min_intv, and the leaf is strict
+ * or level k + 2 is complete (which implies it); smem_kmer_probe_depth's
+ * answer otherwise and whenever leaf == 0.  It reads mn[1 .. k] only and
+ * answers at most 15.  smem_gpu_kmer_probe_depth returns it for the handle's
+ * table, so it may be k + 1.  smem_gpu_kmer_leaf_facts: *level k + 1 (0: the
+ * handle's table has no leaf, and the other three are 0), *leaf_min its
+ * smallest size, *strict, *next_min (any may be NULL). */
+int  smem_gpu_set_kmer_table_leaf(smem_gpu_t *gpu, int k);
+int  smem_kmer_leaf_probe_depth(const uint64_t *mn, int k, uint64_t min_next, int leaf, int leaf_strict,
+                                uint64_t leaf_next, int64_t min_intv);
+int  smem_gpu_kmer_leaf_facts(smem_gpu_t *gpu, int *level, uint64_t *leaf_min, int *strict, uint64_t *next_min);
 /* variant 9 (stamped diagnostic build): copy the per-wave cycle split
  * {advance, fetch, compute, iterations, active lanes, t0, t1, 0} of the last
  * run; returns the number of words copied or a negative code */
