@@ -34,6 +34,7 @@
 
 #include "smem_gpu.h"
 #include "smem_kernels.h"
+#include "occ_rank.h"
 #include "chain_kernels.h"
 #include "ksw_kernels.h"
 #include "aln_kernels.h"
@@ -302,6 +303,9 @@ constexpr uint32_t CHAIN_HEAVY_MIN = 16, CHAIN_GIANT_MIN = 2048, CHAIN_HEAVY_LDS
 // the plain kernel, whatever tables the handle holds
 constexpr int kSeedDefault = 49;
 constexpr int kSeedSkip = 68;
+// 68 with the extend's counts in 64 bits: an index in which a base occurs 2^32 times or more
+// (smem_occ_narrow_ok), or SMEM_GPU_OCC_WIDE=1 when the handle is made
+constexpr int kSeedSkipWide = 71;
 // the k-mer table a handle builds for itself (SMEM_GPU_KMER_K: another depth, 0: none)
 constexpr int kKmerDefault = 12;
 // the persistent grid's lanes per CU when the caller sets none: 4 blocks of 256
@@ -312,7 +316,7 @@ static int seed_lanes_per_cu(int variant) {
     switch (variant) {
         case 44: case 45: case 46: case 49: case 50: case 51: case 52: case 53: case 54: case 56: case 57:
         case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67:
-        case 68: case 69: case 70: return 960;
+        case 68: case 69: case 70: case 71: return 960;
         default: return 768;
     }
 }
@@ -322,7 +326,7 @@ static int seed_owners_per_wave(int variant) {
     switch (variant) {
         case 40: case 41: case 43: case 45: case 47: case 55: case 69: return 32;
         case 42: case 44: case 48: case 49: case 51: case 52: case 54: case 56: case 57:
-        case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: case 68: return 24;
+        case 58: case 59: case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: case 68: case 71: return 24;
         case 46: case 53: case 70: return 28;
         case 50: return 20;
         default: return 64;
@@ -343,6 +347,7 @@ struct smem_gpu {
     int intv_cap = 0;
     int variant = kSeedDefault;  // see smem_gpu_set_kernel_variant
     bool plain49 = false;        // 49 was asked for by number: never run 68 in its place
+    bool occ_wide = false;       // the skipping kernel's 64-bit instantiation (71) in 68's place
     uint32_t* d_bwt = nullptr;      // reference layout (A/B variants 3, 4; freed after the Occ64 re-layout otherwise)
     uint32_t* d_occ64 = nullptr;    // Occ64 layout (default kernel)
     uint32_t* d_occ192 = nullptr;   // Occ192 layout (variant 10)
@@ -852,6 +857,32 @@ const char* smem_gpu_build_id(void) { return SMEM_SRC_HASH; }
 #endif
 const char* smem_gpu_kernel_id(void) { return SMEM_KERNEL_HASH; }
 
+// ---- the Occ64 rank on the host (occ_rank.h: the kernels' own inlines)
+int smem_occ_narrow_ok(const uint64_t L2[5]) { return L2 && smem::occ_narrow_ok(L2) ? 1 : 0; }
+
+int smem_occ64_host(const uint32_t* bwt, uint64_t n_ref, uint32_t* out) {
+    if (!bwt || !out) return SMEM_E_ARG;
+    for (uint64_t b = 0; b < 2 * n_ref; ++b) {
+        const smem::Bucket32 v = smem::occ64_bucket(bwt + (b >> 1) * 16, (uint32_t)(b & 1));
+        std::memcpy(out + b * 8, &v.cnt, 16);
+        std::memcpy(out + b * 8 + 4, &v.sym, 16);
+    }
+    return SMEM_OK;
+}
+
+int smem_extend_host(const uint32_t* bucket_k, const uint32_t* bucket_l, uint64_t kk, uint64_t ll, uint64_t a, uint64_t b,
+                     uint64_t s, int c, uint64_t primary, const uint64_t L2[5], int narrow, uint64_t out[3]) {
+    if (!bucket_k || !bucket_l || !L2 || !out || c < 0 || c > 3) return SMEM_E_ARG;
+    smem::Bucket32 vk, vl;
+    std::memcpy(&vk.cnt, bucket_k, 16);
+    std::memcpy(&vk.sym, bucket_k + 4, 16);
+    std::memcpy(&vl.cnt, bucket_l, 16);
+    std::memcpy(&vl.sym, bucket_l + 4, 16);
+    if (narrow) smem::extend_counts32(primary, L2, a, b, s, c, kk, ll, vk, vl, out[0], out[1], out[2]);
+    else smem::extend_counts64<true>(primary, L2, a, b, s, c, kk, ll, vk, vl, out[0], out[1], out[2]);
+    return SMEM_OK;
+}
+
 const char* smem_strerror(int code) {
     if (g_err[0]) return g_err;
     switch (code) {
@@ -901,6 +932,8 @@ static smem_gpu_t* gpu_handle(int device, uint64_t bwt_size, uint64_t primary, c
     g->bwt_size = bwt_size;
     g->primary = primary;
     std::memcpy(g->L2, L2, sizeof(g->L2));
+    g->occ_wide = !smem_occ_narrow_ok(L2);
+    if (const char* v = getenv("SMEM_GPU_OCC_WIDE")) g->occ_wide = g->occ_wide || atoi(v) != 0;
     return g;
 }
 
@@ -1021,7 +1054,7 @@ int smem_gpu_set_lanes_per_cu(smem_gpu_t* g, int lanes_per_cu) {
 
 int smem_gpu_set_kernel_variant(smem_gpu_t* g, int variant) {
     g_err[0] = 0;
-    if (!g || !(variant == 0 || (variant >= 2 && variant <= 31) || (variant >= 40 && variant <= 70)))
+    if (!g || !(variant == 0 || (variant >= 2 && variant <= 31) || (variant >= 40 && variant <= 71)))
         return fail(SMEM_E_ARG, "smem_gpu_set_kernel_variant");
 
     if (!smem_seed_variant_built(variant))
@@ -1054,7 +1087,8 @@ int smem_gpu_get_kernel_variant(const smem_gpu_t* g) { return g ? g->variant : S
 // the instantiation a launch runs: the default's shape with the short entries virtual where the
 // handle's table allows it (a depth below 2 skips nothing)
 static int seed_run_variant(const smem_gpu_t* g) {
-    return g->variant == kSeedDefault && !g->plain49 && g->d_kt && g->kt_d >= 2 ? kSeedSkip : g->variant;
+    if (g->variant == kSeedDefault && !g->plain49 && g->d_kt && g->kt_d >= 2) return g->occ_wide ? kSeedSkipWide : kSeedSkip;
+    return g->variant == kSeedSkip && g->occ_wide ? kSeedSkipWide : g->variant;  // (68 by number: never narrow where it is not exact)
 }
 
 int smem_gpu_seed_kernel(smem_gpu_t* g) {

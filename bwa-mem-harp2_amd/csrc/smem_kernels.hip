@@ -29,21 +29,9 @@
 #include <string.h>
 #include <algorithm>
 #include "smem_kernels.h"
+#include "occ_rank.h"
 
 namespace smem {
-
-// one of four by a compare chain (the SA walk and the table builders; in seed_wp_kernel only the A/B
-// twin of sel4b below)
-__device__ __forceinline__ uint64_t sel4(int c, uint64_t a, uint64_t b, uint64_t d, uint64_t e) {
-    return c == 0 ? a : (c == 1 ? b : (c == 2 ? d : e));
-}
-
-// sel4 as two bit tests of c (0..3): v_cndmask only, where the compare chain above becomes a branch tree
-__device__ __forceinline__ uint64_t sel4b(int c, uint64_t a, uint64_t b, uint64_t d, uint64_t e) {
-    const bool b0 = c & 1, b1 = c & 2;
-    const uint64_t lo = b0 ? b : a, hi = b0 ? e : d;
-    return b1 ? hi : lo;
-}
 
 // ---- packed list entries (forward / prev / curr lists): 16 B instead of 32 B.
 // x0, x1, x2 < 2^34 (seq_len checked on the host), query end < 2^26.
@@ -122,38 +110,6 @@ __device__ __forceinline__ const uint32_t* boff(const uint32_t* __restrict__ bwt
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-// ---- Occ64: the index re-laid for the GPU as one 32-B bucket per 64 BWT
-// symbols (same 0.5 B/symbol as the reference's 64 B per 128).  Words 0-2:
-// Occ(C), Occ(G), Occ(T) before the bucket, low 32 bits; word 3: their bits
-// 32-33 (C | G << 2 | T << 4); words 4-7: the 64 symbols, 16 per word,
-// MSB-first as in the reference (software/bwt.h:71-78).  Occ(A) is implied:
-// the $ row is not in the BWT, so A + C + G + T = position.  A rank then reads
-// one 32-B bucket and popcounts at most 4 words.
-struct Bucket32 {
-    uint4 cnt, sym;
-};
-
-__device__ __forceinline__ uint64_t occ_cgt(const uint4& c, int i) {
-    const uint32_t lo = i == 0 ? c.x : (i == 1 ? c.y : c.z);
-    return (uint64_t)((c.w >> (2 * i)) & 3) << 32 | lo;
-}
-
-// C, G, T among the first pos+1 (pos < 64) symbols of the bucket: the 64
-// MSB-first 2-bit symbols as two 64-bit halves, each masked to its share of
-// the prefix by one shift (8 fewer VALU per rank than four masked words)
-__device__ __forceinline__ void count_cgt4(const uint4& v, uint32_t pos, uint32_t& C, uint32_t& G, uint32_t& T) {
-    const uint64_t a = (uint64_t)v.x << 32 | v.y, b = (uint64_t)v.z << 32 | v.w;
-    const uint32_t n = pos + 1;  // symbols counted, 1..64
-    const uint64_t ma = n >= 32 ? ~0ull : ~0ull << (64 - 2 * n);
-    const uint64_t mb = n <= 32 ? 0ull : ~0ull << (128 - 2 * n);
-    const uint64_t xa = a & ma, xb = b & mb;
-    constexpr uint64_t K = 0x5555555555555555ull;
-    const uint64_t loa = xa & K, hia = (xa >> 1) & K, lob = xb & K, hib = (xb >> 1) & K;
-    T = __popcll(loa & hia) + __popcll(lob & hib);
-    C = __popcll(loa) + __popcll(lob) - T;
-    G = __popcll(hia) + __popcll(hib) - T;
-}
-
 // ---- Occ192: 64-B lines of 192 BWT symbols (a third fewer index bytes than
 // Occ64, and more k / l pairs in one line).  Chunk 0: Occ(C), Occ(G), Occ(T)
 // before the line's second 64-symbol block (34 bits: low 32 in words 0-2,
@@ -182,43 +138,15 @@ __device__ __forceinline__ void rank192(const Bucket32& v, uint64_t kk, uint64_t
     }
 }
 
-// One bwt_extend in one direction on Occ64 buckets (or Occ192 lines), returning only the child for
-// base c, from the buckets of k = a-1 and l = k+s (kk, ll: the same rows without the $ row):
-//   a: coordinate searched through the BWT (x[1] forward, x[0] backward), b: the other, s: the size
-//   -> na = L2[c] + 1 + Occ(c, k), ns = Occ(c, l) - Occ(c, k),
-//      nb = b + [$ in interval] + sum_{c' > c} (Occ(c', l) - Occ(c', k))
-// (software/bwt.c:416-429; the four-way cumulative in :425-428 restricted to the child taken).
-// BSEL: the selects by c as bit tests (sel4b) and the sum over c' > c as suffix sums
-template <bool L192 = false, bool BSEL = false>
-__device__ __forceinline__ void extend_counts64(const SeedParams& P, uint64_t a, uint64_t b, uint64_t s, int c,
-                                                uint64_t kk, uint64_t ll, const Bucket32& vk, const Bucket32& vl,
-                                                uint64_t& na, uint64_t& nb, uint64_t& ns) {
+// extend_counts64 (occ_rank.h) on Occ192 lines
+template <bool BSEL = false>
+__device__ __forceinline__ void extend_counts192(uint64_t primary, const uint64_t* L2, uint64_t a, uint64_t b, uint64_t s,
+                                                 int c, uint64_t kk, uint64_t ll, const Bucket32& vk, const Bucket32& vl,
+                                                 uint64_t& na, uint64_t& nb, uint64_t& ns) {
     uint64_t tk1, tk2, tk3, tl1, tl2, tl3;
-    if constexpr (L192) {
-        rank192(vk, kk, tk1, tk2, tk3);
-        rank192(vl, ll, tl1, tl2, tl3);
-    } else {
-        uint32_t Ck, Gk, Tk, Cl, Gl, Tl;
-        count_cgt4(vk.sym, (uint32_t)(kk & 63), Ck, Gk, Tk);
-        count_cgt4(vl.sym, (uint32_t)(ll & 63), Cl, Gl, Tl);
-        tk1 = occ_cgt(vk.cnt, 0) + Ck, tk2 = occ_cgt(vk.cnt, 1) + Gk, tk3 = occ_cgt(vk.cnt, 2) + Tk;
-        tl1 = occ_cgt(vl.cnt, 0) + Cl, tl2 = occ_cgt(vl.cnt, 1) + Gl, tl3 = occ_cgt(vl.cnt, 2) + Tl;
-    }
-    const uint64_t tk0 = kk + 1 - tk1 - tk2 - tk3, tl0 = ll + 1 - tl1 - tl2 - tl3;
-    const uint64_t d0 = tl0 - tk0, d1 = tl1 - tk1, d2 = tl2 - tk2, d3 = tl3 - tk3;
-    if constexpr (BSEL) {  // the selects by c's two bits; the suffix sums once, then one select
-        const uint64_t L2c = sel4b(c, P.L2[0], P.L2[1], P.L2[2], P.L2[3]);
-        na = L2c + 1 + sel4b(c, tk0, tk1, tk2, tk3);
-        ns = sel4b(c, d0, d1, d2, d3);
-        const uint64_t g2 = d2 + d3, g1 = d1 + g2;
-        nb = b + (uint64_t)(a <= P.primary && a + s - 1 >= P.primary) + sel4b(c, g1, g2, d3, 0);
-        return;
-    }
-    const uint64_t L2c = sel4(c, P.L2[0], P.L2[1], P.L2[2], P.L2[3]);
-    na = L2c + 1 + sel4(c, tk0, tk1, tk2, tk3);
-    ns = sel4(c, d0, d1, d2, d3);
-    const uint64_t gt = (c < 1 ? d1 : 0) + (c < 2 ? d2 : 0) + (c < 3 ? d3 : 0);
-    nb = b + (uint64_t)(a <= P.primary && a + s - 1 >= P.primary) + gt;
+    rank192(vk, kk, tk1, tk2, tk3);
+    rank192(vl, ll, tl1, tl2, tl3);
+    extend_from_occ<BSEL>(primary, L2, a, b, s, c, kk, ll, tk1, tk2, tk3, tl1, tl2, tl3, na, nb, ns);
 }
 
 // the two 16-B chunks of 64-symbol block b: Occ64 bucket b, or Occ192 line b / 3
@@ -413,7 +341,10 @@ __device__ __forceinline__ void wave_lds_fence() {
 // the record.  dp < 2: the call runs the plain path.  (No loops over bases or levels in the owners'
 // blocks, and no further WP_EMIT site: the first version had them and doubled the launch's SALU)
 // (the body of both kernels below: seed_wp_kernel keeps its eight parameters and its symbol)
-template <int OWN, int NL, int PRIO, int WPE, bool PAIR, bool KT, bool DPOS, int OPT, bool SKIP>
+// WIDE (SKIP only; the other arms are always wide): the extend's counts in 64 bits (extend_counts64), for an
+// index in which a base occurs 2^32 times or more; else in 32 (extend_counts32; the host's rule is
+// smem_occ_narrow_ok)
+template <int OWN, int NL, int PRIO, int WPE, bool PAIR, bool KT, bool DPOS, int OPT, bool SKIP, bool WIDE = true>
 __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
     constexpr int DIET = ~OPT;  // bits 16-128 of OPT take an arm of the diet out
     static_assert(!SKIP || (KT && !PAIR && !DPOS), "SKIP probes the k-mer table and keeps prev_n | dp << 24 in the descriptor");
@@ -1074,10 +1005,15 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
             if (task) {
                 const Bucket32 wk{k0, k1};
                 const Bucket32 wl = bl != bk ? Bucket32{l0, l1} : wk;
-                extend_counts64<false, (DIET & 64) != 0>(P, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
-                na = ktp ? (fwdreq ? p_x1(k0) : p_x0(k0)) : na;
-                nb = ktp ? (fwdreq ? p_x0(k0) : p_x1(k0)) : nb;
-                ns = ktp ? p_x2(k0) : ns;
+                if constexpr (WIDE) extend_counts64<(DIET & 64) != 0>(P.primary, P.L2, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
+                else extend_counts32(P.primary, P.L2, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
+                // (the probe's sides as values of their own: with the unpacking left inside the selects' arms
+                // they became a branch tree over ktp and fwdreq once the extend was the 32-bit one)
+                const uint64_t t0 = p_x0(k0), t1 = p_x1(k0), t2 = p_x2(k0);
+                const uint64_t ta = fwdreq ? t1 : t0, tb = fwdreq ? t0 : t1;
+                na = ktp ? ta : na;
+                nb = ktp ? tb : nb;
+                ns = ktp ? t2 : ns;
             }
         } else if (ktp) {  // forward: na is the x[1] side, backward: the x[0] side
             na = fwdreq ? p_x1(k0) : p_x0(k0);
@@ -1086,14 +1022,14 @@ __device__ __forceinline__ void seed_wp_body(const SeedParams& P) {
         } else if (task) {
             const Bucket32 wk{k0, k1};
             const Bucket32 wl = bl != bk ? Bucket32{l0, l1} : wk;
-            extend_counts64<false, (DIET & 64) != 0>(P, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
+            extend_counts64<(DIET & 64) != 0>(P.primary, P.L2, ra, rb, rs, rc, kk, ll, wk, wl, na, nb, ns);
         }
         uint64_t na2 = 0, nb2 = 0, ns2 = 0;
         if constexpr (PAIR) {
             if (has2) {
                 const Bucket32 wk{m0, m1};
                 const Bucket32 wl = bl2 != bk2 ? Bucket32{n0, n1} : wk;
-                extend_counts64<false>(P, ra2, rb2, rs2, rc, kk2, ll2, wk, wl, na2, nb2, ns2);
+                extend_counts64<false>(P.primary, P.L2, ra2, rb2, rs2, rc, kk2, ll2, wk, wl, na2, nb2, ns2);
             }
         }
         // ---- the backward results: survive, dedup, rank, write into curr ----
@@ -1170,9 +1106,9 @@ __global__ __launch_bounds__(256, WPE) void seed_wp_kernel(SeedParams P) {
 }
 
 // the same with the short entries virtual (SKIP; reads the k-mer table, every OPT bit)
-template <int OWN, int NL, int PRIO, int WPE>
+template <int OWN, int NL, int PRIO, int WPE, bool WIDE = true>
 __global__ __launch_bounds__(256, WPE) void seed_wp_kernel_skip(SeedParams P) {
-    seed_wp_body<OWN, NL, PRIO, WPE, false, true, false, 15, true>(P);
+    seed_wp_body<OWN, NL, PRIO, WPE, false, true, false, 15, true, WIDE>(P);
 }
 
 // Raw logs -> the lists smem_next2 returns: reverse each bwt_smem1 output
@@ -1256,17 +1192,17 @@ __global__ void ovf_slot_kernel(const int32_t* __restrict__ items, int n_ovf, in
 // The product build instantiates the kernel a handle on its default runs (seed_wp_kernel
 // variant 68: 49's shape with the short entries virtual; smem_gpu.cpp seed_run_variant),
 // 49 itself (the plain kernel: a handle without a usable k-mer table, or 49 asked for by
-// number) and 49's k-mer table twin (54).  The other seed_wp_kernel
-// shapes and OPT-bit twins (40-70 other than 49 / 54 / 68;
+// number), 49's k-mer table twin (54) and 68 with the extend's counts in 64 bits (71).  The
+// other seed_wp_kernel shapes and OPT-bit twins (40-70 other than 49 / 54 / 68;
 // DESIGN.md §5) are compiled only with SMEM_AB_VARIANTS (make AB=1): the
 // library ships no kernel whose numbers are already recorded.  (Rounds 1-4's
 // one-lane-per-read seed_kernel, variants 2-31, wrote the raw log format of
 // its time and left with it; its numbers are in DESIGN.md §5.)
 extern "C" int smem_seed_variant_built(int variant) {
 #ifdef SMEM_AB_VARIANTS
-    return variant == 0 || (variant >= 40 && variant <= 70);
+    return variant == 0 || (variant >= 40 && variant <= 71);
 #else
-    return variant == 0 || variant == 49 || variant == 54 || variant == 68;
+    return variant == 0 || variant == 49 || variant == 54 || variant == 68 || variant == 71;
 #endif
 }
 
@@ -1313,14 +1249,17 @@ extern "C" hipError_t smem_launch_seed(const smem::SeedParams* P, int grid, int 
         case 65: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 79>), dim3(grid), dim3(block), 0, st, *P); break;
         case 66: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 143>), dim3(grid), dim3(block), 0, st, *P); break;
         case 67: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, false, false, 255>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 69-70: 68 (virtual short entries) with more owners and shorter lists: <32, 12>, <28, 14>
+        // 69-70: 71 (virtual short entries, 64-bit counts) with more owners and shorter lists: <32, 12>, <28, 14>
         case 69: hipLaunchKernelGGL((smem::seed_wp_kernel_skip<32, 12, 1, 4>), dim3(grid), dim3(block), 0, st, *P); break;
         case 70: hipLaunchKernelGGL((smem::seed_wp_kernel_skip<28, 14, 1, 4>), dim3(grid), dim3(block), 0, st, *P); break;
 #endif
         // 54: the default's shape with the k-mer table (KT; smem_gpu_set_kmer_table, no table: plain)
         case 54: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4, false, true>), dim3(grid), dim3(block), 0, st, *P); break;
-        // 68: 49's shape with the short entries virtual (SKIP; no table: 49's path)
-        case 68: hipLaunchKernelGGL((smem::seed_wp_kernel_skip<24, 18, 1, 4>), dim3(grid), dim3(block), 0, st, *P); break;
+        // 68: 49's shape with the short entries virtual (SKIP; no table: 49's path) and the extend's counts
+        // in 32 bits; 71: the same with the counts in 64 bits (an index with 2^32 or more of one base, or
+        // SMEM_GPU_OCC_WIDE=1; smem_gpu.cpp seed_run_variant)
+        case 68: hipLaunchKernelGGL((smem::seed_wp_kernel_skip<24, 18, 1, 4, false>), dim3(grid), dim3(block), 0, st, *P); break;
+        case 71: hipLaunchKernelGGL((smem::seed_wp_kernel_skip<24, 18, 1, 4, true>), dim3(grid), dim3(block), 0, st, *P); break;
         // 49 (and any number this build does not have): seed_wp_kernel<24 owners per wave, 18 LDS list
         // entries per owner, wave priority, 4 blocks per CU> with every OPT bit
         default: hipLaunchKernelGGL((smem::seed_wp_kernel<24, 18, 1, 4>), dim3(grid), dim3(block), 0, st, *P); break;
@@ -1490,28 +1429,15 @@ extern "C" hipError_t smem_launch_offsets(const uint64_t* in, uint64_t* out, int
 
 namespace smem {
 // reference interleaved buckets (software/bwtindex.c:128-150: 4 x u64 Occ +
-// 8 x u32 symbols per 128) -> Occ64 (see Bucket32); one thread per 64 symbols
+// 8 x u32 symbols per 128) -> Occ64 (occ_rank.h: Bucket32, occ64_bucket); one thread per 64 symbols
 __global__ __launch_bounds__(256) void occ64_kernel(const uint32_t* __restrict__ bwt, uint64_t n_ref,
                                                      uint32_t* __restrict__ out) {
     const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= 2 * n_ref) return;
-    const uint32_t* r = bwt + (b >> 1) * 16;
-    uint64_t c1 = (uint64_t)r[3] << 32 | r[2], c2 = (uint64_t)r[5] << 32 | r[4], c3 = (uint64_t)r[7] << 32 | r[6];
-    const uint32_t* sw = r + 8 + (b & 1) * 4;
-    if (b & 1) {  // add the first 64 symbols of the 128-block
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t lo = r[8 + i] & 0x55555555u, hi = (r[8 + i] >> 1) & 0x55555555u;
-            const uint32_t t = __popc(lo & hi);
-            c1 += __popc(lo) - t;
-            c2 += __popc(hi) - t;
-            c3 += t;
-        }
-    }
+    const Bucket32 v = occ64_bucket(bwt + (b >> 1) * 16, (uint32_t)(b & 1));
     uint4* o = reinterpret_cast<uint4*>(out + b * 8);
-    o[0] = make_uint4((uint32_t)c1, (uint32_t)c2, (uint32_t)c3,
-                      (uint32_t)(c1 >> 32) | (uint32_t)(c2 >> 32) << 2 | (uint32_t)(c3 >> 32) << 4);
-    o[1] = make_uint4(sw[0], sw[1], sw[2], sw[3]);
+    o[0] = v.cnt;
+    o[1] = v.sym;
 }
 }  // namespace smem
 
@@ -1537,7 +1463,7 @@ __global__ __launch_bounds__(256) void kmer_table_kernel(SeedParams P, uint4* __
     const Bucket32 vk{o[2 * (kk >> 6)], o[2 * (kk >> 6) + 1]}, vl{o[2 * (ll >> 6)], o[2 * (ll >> 6) + 1]};
     for (int c = 0; c < 4; ++c) {
         uint64_t na, nb, ns;
-        extend_counts64<false>(P, a, b, s, c, kk, ll, vk, vl, na, nb, ns);
+        extend_counts64<false>(P.primary, P.L2, a, b, s, c, kk, ll, vk, vl, na, nb, ns);
         lev[(uint64_t)c << (2 * (L - 1)) | w] = ns ? pack_p(na, nb, ns, 0) : make_uint4(0, 0, 0, 0);
     }
 }
@@ -1589,7 +1515,7 @@ __global__ __launch_bounds__(256) void kmer_next_level_min_kernel(SeedParams P, 
         const Bucket32 vk{o[2 * (kk >> 6)], o[2 * (kk >> 6) + 1]}, vl{o[2 * (ll >> 6)], o[2 * (ll >> 6) + 1]};
         for (int c = 0; c < 4; ++c) {
             uint64_t na, nb, ns;
-            extend_counts64<false>(P, a, b, s, c, kk, ll, vk, vl, na, nb, ns);
+            extend_counts64<false>(P.primary, P.L2, a, b, s, c, kk, ll, vk, vl, na, nb, ns);
             m = ns < m ? ns : m;
             eq |= ns == s;
         }
@@ -1761,9 +1687,8 @@ __global__ __launch_bounds__(256) void sa_walk_kernel(SaParams S) {
             if (k == S.primary) {
                 k = 0;
             } else {
-                const uint32_t pos = (uint32_t)(kk & 63), sel = pos >> 4;
-                const uint32_t w = sel == 0 ? vb.x : (sel == 1 ? vb.y : (sel == 2 ? vb.z : vb.w));
-                const int c = (int)((w >> ((~pos & 15u) << 1)) & 3u);
+                const uint32_t pos = (uint32_t)(kk & 63);
+                const int c = sym_at(vb, pos);
                 uint32_t C, G, T;
                 count_cgt4(vb, pos, C, G, T);
                 const uint64_t oc = occ_cgt(va, 0) + C, og = occ_cgt(va, 1) + G, ot = occ_cgt(va, 2) + T;
@@ -1802,9 +1727,8 @@ __global__ __launch_bounds__(256) void sa_densify_kernel(SaParams S, uint32_t ds
         } else {
             const uint64_t kk = k - (k > S.primary);
             const uint4 va = occ[(kk >> 6) * 2], vb = occ[(kk >> 6) * 2 + 1];
-            const uint32_t pos = (uint32_t)(kk & 63), sel = pos >> 4;
-            const uint32_t w = sel == 0 ? vb.x : (sel == 1 ? vb.y : (sel == 2 ? vb.z : vb.w));
-            const int c = (int)((w >> ((~pos & 15u) << 1)) & 3u);
+            const uint32_t pos = (uint32_t)(kk & 63);
+            const int c = sym_at(vb, pos);
             uint32_t C, G, T;
             count_cgt4(vb, pos, C, G, T);
             const uint64_t oc = occ_cgt(va, 0) + C, og = occ_cgt(va, 1) + G, ot = occ_cgt(va, 2) + T;
@@ -1855,9 +1779,8 @@ __global__ __launch_bounds__(256) void sa_densify_hop_kernel(SaParams S, uint32_
             } else {
                 const uint64_t kk = k - (k > S.primary);
                 const uint4 va = occ[(kk >> 6) * 2], vb = occ[(kk >> 6) * 2 + 1];
-                const uint32_t pos = (uint32_t)(kk & 63), sel = pos >> 4;
-                const uint32_t w = sel == 0 ? vb.x : (sel == 1 ? vb.y : (sel == 2 ? vb.z : vb.w));
-                const int c = (int)((w >> ((~pos & 15u) << 1)) & 3u);
+                const uint32_t pos = (uint32_t)(kk & 63);
+                const int c = sym_at(vb, pos);
                 uint32_t C, G, T;
                 count_cgt4(vb, pos, C, G, T);
                 const uint64_t oc = occ_cgt(va, 0) + C, og = occ_cgt(va, 1) + G, ot = occ_cgt(va, 2) + T;

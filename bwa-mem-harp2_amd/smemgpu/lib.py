@@ -46,6 +46,7 @@ EXPORTED = [
     "smem_gpu_load_contig_names", "smem_batch_set_read_text", "smem_batch_sam", "smem_batch_sam_results",
     "smem_sam_text", "smem_batch_sam_stats",
     "smem_ksw_align2_long", "smem_matesw_opt_default", "smem_matesw", "smem_gpu_cu_count",
+    "smem_occ_narrow_ok", "smem_occ64_host", "smem_extend_host",
 ]
 
 # smem_batch_fetch_mask bits (include/smem_gpu.h)
@@ -394,6 +395,14 @@ def load() -> C.CDLL:
         lib.smem_gpu_kmer_leaf_facts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
                                                  C.POINTER(C.c_uint64)]
         lib.smem_gpu_kmer_leaf_facts.restype = C.c_int
+    if hasattr(lib, "smem_occ_narrow_ok"):  # absent from A/B libraries built before the bit-plane layout
+        lib.smem_occ_narrow_ok.argtypes = [C.c_void_p]
+        lib.smem_occ_narrow_ok.restype = C.c_int
+        lib.smem_occ64_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.smem_occ64_host.restype = C.c_int
+        lib.smem_extend_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                         C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]
+        lib.smem_extend_host.restype = C.c_int
     if hasattr(lib, "smem_batch_debug"):  # absent from older A/B builds
         lib.smem_batch_debug.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     lib.smem_strerror.argtypes = [C.c_int]

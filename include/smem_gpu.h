@@ -786,8 +786,8 @@ int  smem_gpu_set_intv_cap(smem_gpu_t *gpu, int cap_per_read);
  * product build has 0 = 49 (the default, seed_wp_kernel: see
  * smem_gpu_get_kernel_variant below for 40-51), 2 = 20 = 26, 9, 23, 24, 25, 27
  * and 28; the others need a library built with `make AB=1`, else SMEM_E_ARG):
- * 2 (the default of rounds 1-4) Occ64 buckets (32 B per 64 symbols, re-laid on the
- * device at init), per-lane fetch into two register slots with bucket reuse,
+ * 2 (the default of rounds 1-4) Occ64 buckets (32 B per 64 symbols: three counts and
+ * the symbols as two 64-bit bit planes, re-laid on the device at init), per-lane fetch into two register slots with bucket reuse,
  * the first 11 entries of every list in LDS (the forward list as a ring of its
  * last 11 pushes); 11 the same with LDS-DMA slots and 7 list entries; 12 that
  * with 12 LDS entries at 2 blocks per CU; 13 the round-1 default (LDS-DMA
@@ -813,6 +813,10 @@ int  smem_gpu_set_kernel_variant(smem_gpu_t *gpu, int variant);
  * keeps the entries whose strings the handle's k-mer table answers virtual
  * (smem_gpu_kmer_facts), while it holds a table of depth >= 2;
  * smem_gpu_seed_kernel returns the instantiation the next launch runs.
+ * 68 does the extend's rank arithmetic in 32 bits, which is exact while every
+ * base occurs fewer than 2^32 times in the BWT (smem_occ_narrow_ok below); a
+ * handle on another index, or made with SMEM_GPU_OCC_WIDE=1 in the
+ * environment, runs 71 in its place: the same kernel with 64-bit counts.
  * 49 set by number (or SMEM_GPU_SEED_VARIANT=49) is the plain kernel, in every
  * build, for A/B; 68 by number runs it whatever the table (none: 49's path).
  * Mind the collision: the number this getter reports for a default handle (49)
@@ -893,6 +897,23 @@ int  smem_gpu_set_kmer_table_leaf(smem_gpu_t *gpu, int k);
 int  smem_kmer_leaf_probe_depth(const uint64_t *mn, int k, uint64_t min_next, int leaf, int leaf_strict,
                                 uint64_t leaf_next, int64_t min_intv);
 int  smem_gpu_kmer_leaf_facts(smem_gpu_t *gpu, int *level, uint64_t *leaf_min, int *strict, uint64_t *next_min);
+/* The Occ64 rank on the host (diagnostics; no device is touched): the code of
+ * the kernels, compiled for the CPU, so that its arithmetic can be checked on
+ * counts no small index reaches.  smem_occ_narrow_ok: 1 when every base
+ * occurs fewer than 2^32 times (L2[c + 1] - L2[c] < 2^32, c = 0..3), the
+ * condition under which the seeding kernel's 32-bit extend is exact.
+ * smem_occ64_host: the Occ64 layout (2 * n_ref buckets of 8 words into out)
+ * of n_ref reference buckets of 16 words, as the device builds it at load.
+ * smem_extend_host: one bwt_extend for base c (0..3) of the interval (a, b, s)
+ * from the two Occ64 buckets (8 words each; the same pointer when k and l
+ * share one) of rows kk = k - (k >= primary) and ll, k = a - 1, l = k + s;
+ * narrow != 0: the 32-bit form.  out: the child's a-side start, b-side start
+ * and size. */
+int  smem_occ_narrow_ok(const uint64_t L2[5]);
+int  smem_occ64_host(const uint32_t *bwt, uint64_t n_ref, uint32_t *out);
+int  smem_extend_host(const uint32_t *bucket_k, const uint32_t *bucket_l, uint64_t kk, uint64_t ll, uint64_t a,
+                      uint64_t b, uint64_t s, int c, uint64_t primary, const uint64_t L2[5], int narrow,
+                      uint64_t out[3]);
 /* variant 9 (stamped diagnostic build): copy the per-wave cycle split
  * {advance, fetch, compute, iterations, active lanes, t0, t1, 0} of the last
  * run; returns the number of words copied or a negative code */
@@ -903,7 +924,7 @@ const char *smem_strerror(int code);
  * loaded is the build of the sources beside it */
 const char *smem_gpu_build_id(void);
 /* hash of the seeding kernel's own sources and compile flags only
- * (csrc/smem_kernels.hip / .h): a counter profile of seed_kernel recorded on
+ * (csrc/smem_kernels.hip / .h, csrc/occ_rank.h): a counter profile of seed_kernel recorded on
  * another build of the runtime still describes this one when it matches */
 const char *smem_gpu_kernel_id(void);
 
