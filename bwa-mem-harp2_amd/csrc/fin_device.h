@@ -1,7 +1,7 @@
-// What the region stages share (fin_kernels.hip, matesw_kernels.hip): one read's regions as a
-// view in LDS, ks_introsort and its parts comparison for comparison over a permutation, the
-// redundancy test and mem_sort_and_dedup by one wave.  Both files are compiled with
-// -ffp-contract=off (see fin_kernels.hip).
+// What the region stages share (fin_kernels.hip, matesw_kernels.hip, pair_kernels.hip): one
+// read's regions as a view in LDS, ks_introsort and its parts comparison for comparison over a
+// permutation, the redundancy test and mem_sort_and_dedup by one wave, hash_64, mem_infer_dir and
+// mem_approx_mapq_se.  All three files are compiled with -ffp-contract=off (see fin_kernels.hip).
 #pragma once
 #include "fin_kernels.h"
 
@@ -9,6 +9,26 @@ namespace smem {
 namespace {
 
 constexpr int FIN_STK = 16;  // pending introsort segments: log2(FIN_MAX_REGS / 16) + 1 = 7 at most
+
+__device__ __forceinline__ uint64_t fin_hash_64(uint64_t key) {  // software/utils.h:99-110
+    key += ~(key << 32);
+    key ^= (key >> 22);
+    key += ~(key << 13);
+    key ^= (key >> 8);
+    key += (key << 3);
+    key ^= (key >> 15);
+    key += ~(key << 27);
+    key ^= (key >> 31);
+    return key;
+}
+
+// mem_infer_dir (software/bwamem_pair.c:23-30)
+__device__ __forceinline__ int pe_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t& dist) {
+    const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
+    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
+    dist = p2 > b1 ? p2 - b1 : b1 - p2;
+    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
+}
 
 // One read's regions in LDS, element i of an array at [i * S]: S = 1 for the
 // wave tier (the block holds one read), S = 64 for the lane tier (the pointers
@@ -190,6 +210,58 @@ __device__ __forceinline__ bool fin_redundant(float mlr, int64_t prb, int64_t pr
     return (float)orr > mlr * (float)mr && (float)oq > mlr * (float)mq;
 }
 
+// mem_approx_mapq_se (software/bwamem.c:1333-1356); -1 where a table ends or l < 1.  PT: FinParams, or
+// the pairing stage's parameters, which carry the same options and tables under the same names
+template <class PT>
+__device__ int fin_mapq(const PT& P, int score, int sub0, int csub, int l, int seedcov, int sub_n) {
+#pragma clang fp contract(off)
+    int sub = sub0 ? sub0 : P.min_seed_len * P.a;
+    sub = csub > sub ? csub : sub;
+    if (sub >= score) return 0;
+    if (l < 1) return -1;
+    const double identity = 1. - (double)(l * P.a - score) / (double)(P.a + P.b) / (double)l;
+    int mapq;
+    if (score == 0) {
+        mapq = 0;
+    } else if (P.mapQ_coef_len > 0.f) {
+        double tmp;
+        if ((float)l < P.mapQ_coef_len) {
+            tmp = 1.;
+        } else {
+            if (l < 2 || l >= FIN_TAB_LEN) return -1;
+            tmp = (double)P.mapQ_coef_fac / P.log_tab[l];
+        }
+        const double id2 = identity * identity;
+        tmp = tmp * id2;
+        double x = 6.02 * (double)(score - sub);
+        x = x / (double)P.a;
+        x = x * tmp;
+        x = x * tmp;
+        x = x + .499;
+        mapq = (int)x;
+    } else {
+        if (seedcov < 1 || seedcov >= FIN_TAB_LEN) return -1;
+        double x = 1. - (double)sub / (double)score;
+        x = 30.0 * x;
+        x = x * P.log_tab[seedcov];
+        x = x + .499;
+        mapq = (int)x;
+        if (identity < 0.95) {
+            double y = (double)mapq * identity;
+            y = y * identity;
+            y = y + .499;
+            mapq = (int)y;
+        }
+    }
+    if (sub_n > 0) {
+        if (sub_n >= FIN_TAB_LEN) return -1;
+        mapq -= P.subn_tab[sub_n];
+    }
+    if (mapq > 60) mapq = 60;
+    if (mapq < 0) mapq = 0;
+    return mapq;
+}
+
 // keep the positions of [from, n) whose region passes `keep`, in order, behind [0, from);
 // in place: a chunk is read before it is written, and writes never pass the chunk
 template <class KEEP>
@@ -211,7 +283,7 @@ __device__ uint32_t fin_compact_wave(const View<1>& v, uint32_t from, uint32_t n
 
 // mem_sort_and_dedup (software/bwamem.c:705-746) of the n > 1 regions a wave tier view holds, by
 // the one wave of its block: the kept regions' count, their order in v.P
-__device__ uint32_t fin_sort_dedup_wave(const View<1>& v, uint32_t n, float mlr, uint32_t* stk, int lane) {
+[[maybe_unused]] __device__ uint32_t fin_sort_dedup_wave(const View<1>& v, uint32_t n, float mlr, uint32_t* stk, int lane) {
     if (lane == 0) fin_introsort<false>(v, n, LtRe<1>{v}, stk);
     __syncthreads();
     for (uint32_t i = 1; i < n; ++i) {

@@ -12,24 +12,13 @@
 // (:1340-1352).  This file is compiled with -ffp-contract=off and the
 // functions below say so again: a fused multiply-add would round once where
 // the host rounds twice.  log() comes from tables the host filled with its own
-// libm; the division by log(l) is an IEEE division on both sides.
+// libm; the division by log(l) is an IEEE division on both sides (fin_mapq, in
+// fin_device.h: the pairing stage calls it too).
 #include "fin_kernels.h"
 #include "fin_device.h"
 
 namespace smem {
 namespace {
-
-__device__ __forceinline__ uint64_t hash_64(uint64_t key) {  // software/utils.h:99-110
-    key += ~(key << 32);
-    key ^= (key >> 22);
-    key += ~(key << 13);
-    key ^= (key >> 8);
-    key += (key << 3);
-    key ^= (key >> 15);
-    key += ~(key << 27);
-    key ^= (key >> 31);
-    return key;
-}
 
 // the third order (software/bwamem.c:696-703), over regions
 template <int S>
@@ -49,56 +38,6 @@ __device__ __forceinline__ bool fin_overlaps(float ml, int jqb, int jqe, int iqb
     if (e_min <= b_max) return false;
     const int min_l = iqe - iqb < jqe - jqb ? iqe - iqb : jqe - jqb;
     return (float)(e_min - b_max) >= (float)min_l * ml;
-}
-
-// mem_approx_mapq_se (software/bwamem.c:1333-1356); -1 where a table ends or l < 1
-__device__ int fin_mapq(const FinParams& P, int score, int sub0, int csub, int l, int seedcov, int sub_n) {
-#pragma clang fp contract(off)
-    int sub = sub0 ? sub0 : P.min_seed_len * P.a;
-    sub = csub > sub ? csub : sub;
-    if (sub >= score) return 0;
-    if (l < 1) return -1;
-    const double identity = 1. - (double)(l * P.a - score) / (double)(P.a + P.b) / (double)l;
-    int mapq;
-    if (score == 0) {
-        mapq = 0;
-    } else if (P.mapQ_coef_len > 0.f) {
-        double tmp;
-        if ((float)l < P.mapQ_coef_len) {
-            tmp = 1.;
-        } else {
-            if (l < 2 || l >= FIN_TAB_LEN) return -1;
-            tmp = (double)P.mapQ_coef_fac / P.log_tab[l];
-        }
-        const double id2 = identity * identity;
-        tmp = tmp * id2;
-        double x = 6.02 * (double)(score - sub);
-        x = x / (double)P.a;
-        x = x * tmp;
-        x = x * tmp;
-        x = x + .499;
-        mapq = (int)x;
-    } else {
-        if (seedcov < 1 || seedcov >= FIN_TAB_LEN) return -1;
-        double x = 1. - (double)sub / (double)score;
-        x = 30.0 * x;
-        x = x * P.log_tab[seedcov];
-        x = x + .499;
-        mapq = (int)x;
-        if (identity < 0.95) {
-            double y = (double)mapq * identity;
-            y = y * identity;
-            y = y + .499;
-            mapq = (int)y;
-        }
-    }
-    if (sub_n > 0) {
-        if (sub_n >= FIN_TAB_LEN) return -1;
-        mapq -= P.subn_tab[sub_n];
-    }
-    if (mapq > 60) mapq = 60;
-    if (mapq < 0) mapq = 0;
-    return mapq;
 }
 
 struct ReadArgs {
@@ -209,7 +148,7 @@ __device__ void fin_read_lane(const FinParams& P, const View<S>& v0, uint32_t* s
         for (uint32_t k = 0; k < n; ++k) {
             const uint32_t x = v.P(k);
             const int rlen = (int)(v.KA(x) - v.KB(x));
-            v.KA(x) = (int64_t)hash_64((uint64_t)(A.id + (int64_t)k));
+            v.KA(x) = (int64_t)fin_hash_64((uint64_t)(A.id + (int64_t)k));
             v.RLEN(x) = rlen;
         }
         fin_introsort<SMALL>(v, n, LtHash<S>{v}, stk);
@@ -271,7 +210,7 @@ __device__ void fin_read_wave(const FinParams& P, const View<1>& v0, uint32_t* s
         for (uint32_t k = (uint32_t)lane; k < n; k += 64) {
             const uint32_t x = v.P(k);
             const int rlen = (int)(v.KA(x) - v.KB(x));
-            v.KA(x) = (int64_t)hash_64((uint64_t)(A.id + (int64_t)k));
+            v.KA(x) = (int64_t)fin_hash_64((uint64_t)(A.id + (int64_t)k));
             v.RLEN(x) = rlen;
         }
         __syncthreads();

@@ -38,14 +38,6 @@ __device__ __forceinline__ int pac_at(const uint8_t* pac, int64_t l) {
     return pac[l >> 2] >> ((~l & 3) << 1) & 3;  // _get_pac (software/bntseq.h)
 }
 
-// mem_infer_dir (software/bwamem_pair.c:23-30)
-__device__ __forceinline__ int msw_infer_dir(int64_t l_pac, int64_t b1, int64_t b2, int64_t& dist) {
-    const int r1 = b1 >= l_pac, r2 = b2 >= l_pac;
-    const int64_t p2 = r1 == r2 ? b2 : (l_pac << 1) - 1 - b2;
-    dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-
 // pes[r] by selects: a runtime index into the kernel's arguments would copy them to scratch
 __device__ __forceinline__ int msw_low(const MswParams& P, int r) {
     return r == 0 ? P.pes[0].low : r == 1 ? P.pes[1].low : r == 2 ? P.pes[2].low : P.pes[3].low;
@@ -57,7 +49,7 @@ __device__ __forceinline__ int msw_high(const MswParams& P, int r) {
 // bit r set: a region starting at b2 pairs with the anchor at b1 in orientation r (:117-119)
 __device__ __forceinline__ int msw_found(const MswParams& P, int64_t b1, int64_t b2) {
     int64_t dist;
-    const int r = msw_infer_dir(P.l_pac, b1, b2, dist);
+    const int r = pe_infer_dir(P.l_pac, b1, b2, dist);
     return dist >= (int64_t)msw_low(P, r) && dist <= (int64_t)msw_high(P, r) ? 1 << r : 0;
 }
 

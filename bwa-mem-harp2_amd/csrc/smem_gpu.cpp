@@ -42,6 +42,7 @@
 #include "fin_kernels.h"
 #include "sam_kernels.h"
 #include "matesw_kernels.h"
+#include "pair_kernels.h"
 
 using smem::Intv;
 
@@ -100,13 +101,14 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
 // caller resumed.  stage: upload (smem_batch_set_reads*), seed
 // (smem_batch_run), sa, chain, aln (smem_batch_chain2aln), fin (smem_reg_finalize,
 // smem_batch_reg_finalize), g2a (smem_batch_reg2aln), sam (smem_batch_sam, smem_sam_text), matesw (smem_matesw),
+// pair (smem_pestat, smem_pair),
 // fetch, or any.
 // ":sticky" also marks the device faulted, as a real runtime failure does;
 // ":hip=<code>" goes through fail() with that hipError_t, so the
 // classification decides (hip=9, hipErrorInvalidConfiguration: that call only;
 // hip=719, hipErrorLaunchFailure: the device).
-enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_G2A, ST_SAM, ST_MSW, ST_N };
-const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin", "g2a", "sam", "matesw"};
+enum { ST_UPLOAD, ST_SEED, ST_SA, ST_CHAIN, ST_ALN, ST_FETCH, ST_FIN, ST_G2A, ST_SAM, ST_MSW, ST_PAIR, ST_N };
+const char* const k_stage_name[ST_N] = {"upload", "seed", "sa", "chain", "aln", "fetch", "fin", "g2a", "sam", "matesw", "pair"};
 std::atomic<uint64_t> g_stage_calls[ST_N];
 
 int inject_fault(int stage) {
@@ -3547,6 +3549,252 @@ int smem_matesw(smem_gpu_t* g, int n_pairs, const uint8_t* codes, const uint64_t
     HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     HIP_TRY(hipEventElapsedTime(&ms2, ev[2], ev[3]));
     if (kernel_ms) *kernel_ms = (double)ms + (double)ms2;
+    return SMEM_OK;
+}
+
+// ---- insert-size statistics and pairing (mem_pestat, mem_pair and the decision block of
+// mem_sam_pe: csrc/pair_kernels.hip)
+static_assert(sizeof(smem_pair_sel_t) == sizeof(smem::PairSel), "pairing selection layout");
+static_assert(SMEM_PESTAT_MAX_INS == smem::PST_MAX_INS && SMEM_PAIR_TAB_LEN == smem::PAIR_TAB_LEN &&
+              SMEM_PAIR_HOST == smem::PAIR_HOST, "pairing limits");
+
+void smem_pestat_opt_default(smem_pestat_opt_t* o) {  // mem_opt_init (software/bwamem.c:48-75)
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->a = 1, o->min_seed_len = 19, o->max_ins = 10000, o->mask_level = 0.50f;
+}
+
+// mem_pestat's finish (software/bwamem_pair.c:64-106) over hist[4][max_ins + 1], the counts of
+// each insert size per orientation: the sorted array q->a is the histogram read in ascending
+// order, every value as often as it occurs.  Everything is the reference's expression in its
+// order; the sum of squares takes one addition per pair.  Contraction is off in the function, as in
+// the device functions: a target with FMA must not fuse avg - 4.0 * std.
+static void pestat_finish(const uint32_t* hist, int max_ins, smem_pestat_t pes[4], uint64_t n_cand[4]) {
+#pragma clang fp contract(off)   // no fused multiply-add on any host: the reference rounds every product
+    const size_t row = (size_t)max_ins + 1;
+    std::memset(pes, 0, 4 * sizeof(smem_pestat_t));
+    for (int d = 0; d < 4; ++d) {
+        const uint32_t* h = hist + (size_t)d * row;
+        uint64_t n = 0;
+        for (size_t v = 1; v < row; ++v) n += h[v];
+        n_cand[d] = n;
+        smem_pestat_t* r = &pes[d];
+        if (n < 10) {  // MIN_DIR_CNT
+            r->failed = 1;
+            continue;
+        }
+        // q->a[k] for the three percentile indices, ascending
+        const uint64_t want[3] = {(uint64_t)(int)(.25 * n + .499), (uint64_t)(int)(.50 * n + .499),
+                                  (uint64_t)(int)(.75 * n + .499)};
+        int pct[3] = {0, 0, 0};
+        {
+            uint64_t seen = 0;
+            int w = 0;
+            for (size_t v = 1; v < row && w < 3; ++v) {
+                seen += h[v];
+                while (w < 3 && want[w] < seen) pct[w++] = (int)v;
+            }
+        }
+        const int p25 = pct[0], p75 = pct[2];
+        r->low = (int)(p25 - 2.0 * (p75 - p25) + .499);  // OUTLIER_BOUND
+        if (r->low < 1) r->low = 1;
+        r->high = (int)(p75 + 2.0 * (p75 - p25) + .499);
+        const size_t lo = (size_t)r->low, hi = std::min<size_t>((size_t)r->high, row - 1);
+        uint64_t x = 0;
+        r->avg = 0;
+        for (size_t v = lo; v <= hi; ++v)
+            for (uint32_t c = 0; c < h[v]; ++c) r->avg += (double)(uint64_t)v, ++x;
+        r->avg /= (double)x;
+        r->std = 0;
+        for (size_t v = lo; v <= hi; ++v) {
+            const double t = ((double)(uint64_t)v - r->avg) * ((double)(uint64_t)v - r->avg);
+            for (uint32_t c = 0; c < h[v]; ++c) r->std += t;
+        }
+        r->std = std::sqrt(r->std / (double)x);
+        r->low = (int)(p25 - 3.0 * (p75 - p25) + .499);  // MAPPING_BOUND
+        r->high = (int)(p75 + 3.0 * (p75 - p25) + .499);
+        if (r->low > r->avg - 4.0 * r->std) r->low = (int)(r->avg - 4.0 * r->std + .499);   // MAX_STDDEV
+        if (r->high < r->avg - 4.0 * r->std) r->high = (int)(r->avg + 4.0 * r->std + .499);  // as written (:95)
+        if (r->low < 1) r->low = 1;
+    }
+    uint64_t max = 0;
+    for (int d = 0; d < 4; ++d) max = std::max(max, n_cand[d]);
+    for (int d = 0; d < 4; ++d)
+        if (pes[d].failed == 0 && (double)n_cand[d] < (double)max * 0.05) pes[d].failed = 1;  // MIN_DIR_RATIO
+    for (int d = 0; d < 4; ++d)
+        if (pes[d].failed) pes[d].low = pes[d].high = 0, pes[d].avg = pes[d].std = 0;
+}
+
+int smem_pestat(smem_gpu_t* g, int n_pairs, const smem_alnreg_t* regs, const uint64_t* reg_off, int64_t l_pac,
+                const smem_pestat_opt_t* opt, smem_pestat_t pes[4], uint64_t n_cand[4], double* kernel_ms) {
+    g_err[0] = 0;
+    if (!g || n_pairs < 0 || n_pairs > (1 << 29) || !opt || !pes || !n_cand || l_pac <= 0 || (n_pairs > 0 && !reg_off))
+        return fail(SMEM_E_ARG, "smem_pestat: bad arguments");
+    if (opt->max_ins < 1 || opt->max_ins > SMEM_PESTAT_MAX_INS)
+        return fail(SMEM_E_ARG, "smem_pestat: max_ins outside 1 .. SMEM_PESTAT_MAX_INS");
+    if (opt->a < 1 || opt->min_seed_len < 0 || opt->mask_level != opt->mask_level)
+        return fail(SMEM_E_ARG, "smem_pestat: options need a >= 1, min_seed_len >= 0 and a mask_level that is a number");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const size_t n_reads = 2 * (size_t)n_pairs, n_hist = 4 * ((size_t)opt->max_ins + 1);
+    for (size_t r = 0; r < n_reads; ++r)
+        if (reg_off[r + 1] < reg_off[r]) return fail(SMEM_E_ARG, "smem_pestat: reg_off not ascending");
+    const uint64_t r0 = n_pairs ? reg_off[0] : 0, n_regs = n_pairs ? reg_off[n_reads] - r0 : 0;
+    if (n_regs >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_pestat: too many regions");
+    if (n_regs > 0 && !regs) return fail(SMEM_E_ARG, "smem_pestat: no regions");
+    std::vector<uint32_t> hist(n_hist, 0u);
+    if (n_pairs > 0) {
+        DevBuf<smem::AlnReg> dregs;
+        DevBuf<uint64_t> dregoff;
+        DevBuf<uint32_t> dhist;
+        std::vector<uint64_t> off0;
+        Events<2> ev;
+        DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
+        if (call.rc) return call.rc;
+        const hipStream_t st = call.st;
+        HIP_TRY(ev.create());
+        HIP_TRY(dregs.ensure(n_regs));
+        HIP_TRY(dregoff.ensure(n_reads + 1));
+        HIP_TRY(dhist.ensure(n_hist));
+        const uint64_t* h_off = reg_off;
+        if (r0) {  // the kernel indexes regs from 0
+            off0.resize(n_reads + 1);
+            for (size_t r = 0; r <= n_reads; ++r) off0[r] = reg_off[r] - r0;
+            h_off = off0.data();
+        }
+        if (n_regs) HIP_TRY(hipMemcpyAsync(dregs.p, regs + r0, sizeof(smem::AlnReg) * n_regs, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dregoff.p, h_off, 8 * (n_reads + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(dhist.p, 0, sizeof(uint32_t) * n_hist, st));
+        smem::PstParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.regs = dregs.p, P.reg_off = dregoff.p, P.l_pac = l_pac, P.n_pairs = n_pairs;
+        P.a = opt->a, P.min_seed_len = opt->min_seed_len, P.max_ins = opt->max_ins, P.mask_level = opt->mask_level;
+        P.hist = dhist.p;
+        HIP_TRY(hipEventRecord(ev[0], st));
+        HIP_TRY(smem_launch_pst(&P, g->n_cu, st));
+        HIP_TRY(hipEventRecord(ev[1], st));
+        HIP_TRY(hipMemcpyAsync(hist.data(), dhist.p, sizeof(uint32_t) * n_hist, hipMemcpyDeviceToHost, st));
+        INJECT(ST_PAIR);
+        HIP_TRY(hipStreamSynchronize(st));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        if (kernel_ms) *kernel_ms = ms;
+    }
+    pestat_finish(hist.data(), opt->max_ins, pes, n_cand);
+    return SMEM_OK;
+}
+
+void smem_pair_opt_default(smem_pair_opt_t* o) {  // mem_opt_init (software/bwamem.c:48-75)
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->a = 1, o->b = 4, o->o_del = o->o_ins = 6, o->e_del = o->e_ins = 1;
+    o->pen_unpaired = 17, o->T = 30, o->min_seed_len = 19;
+    o->mapQ_coef_len = 50, o->mapQ_coef_fac = (int)std::log(o->mapQ_coef_len);
+}
+
+// one entry of the penalty table: the reference's expression in its order (software/bwamem_pair.c:
+// 210-211), with the host's libm and no contraction
+static double pair_pen(const smem_pestat_t& r, int64_t dist, int a) {
+#pragma clang fp contract(off)
+    const double ns = (dist - r.avg) / r.std;
+    return .721 * std::log(2. * std::erfc(std::fabs(ns) * M_SQRT1_2)) * a;
+}
+
+int smem_pair(smem_gpu_t* g, int n_pairs, const smem_alnreg_t* regs, const uint64_t* reg_off, const int64_t* ids,
+              int64_t id0, int64_t l_pac, const smem_pestat_t pes[4], const smem_pair_opt_t* opt, smem_pair_sel_t* sel,
+              double* kernel_ms) {
+    g_err[0] = 0;
+    if (!g || n_pairs < 0 || n_pairs > (1 << 29) || !opt || !pes || l_pac <= 0 || (n_pairs > 0 && (!reg_off || !sel)))
+        return fail(SMEM_E_ARG, "smem_pair: bad arguments");
+    if (opt->a < 1 || opt->b < 0 || opt->mapQ_coef_len != opt->mapQ_coef_len || (opt->flags & ~SMEM_PAIR_F_NOPAIRING))
+        return fail(SMEM_E_ARG, "smem_pair: options need a >= 1, b >= 0, a mapQ_coef_len that is a number and known flags");
+    // the penalty table, with the host's libm in the reference's order of operations (:210-211)
+    smem::PairDir dirs[4];
+    uint64_t n_tab = 0;
+    for (int d = 0; d < 4; ++d) {
+        dirs[d] = smem::PairDir{pes[d].low, pes[d].high, pes[d].failed ? 1 : 0, 0, n_tab};
+        if (pes[d].failed || pes[d].high < pes[d].low) continue;
+        const int64_t len = (int64_t)pes[d].high - pes[d].low + 1;
+        if (len > SMEM_PAIR_TAB_LEN) return fail(SMEM_E_ARG, "smem_pair: an orientation's range is longer than SMEM_PAIR_TAB_LEN");
+        n_tab += (uint64_t)len;
+    }
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (n_pairs == 0) return SMEM_OK;
+    const size_t n_reads = 2 * (size_t)n_pairs;
+    for (size_t r = 0; r < n_reads; ++r)
+        if (reg_off[r + 1] < reg_off[r]) return fail(SMEM_E_ARG, "smem_pair: reg_off not ascending");
+    const uint64_t r0 = reg_off[0], n_regs = reg_off[n_reads] - r0;
+    if (n_regs >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_pair: too many regions");
+    if (n_regs > 0 && !regs) return fail(SMEM_E_ARG, "smem_pair: no regions");
+    for (size_t r = 0; r < n_reads; ++r) {
+        const int64_t n = (int64_t)(reg_off[r + 1] - reg_off[r]);
+        for (uint64_t k = reg_off[r]; k < reg_off[r + 1]; ++k)
+            if (regs[k].secondary >= n || regs[k].score < 0)
+                return fail(SMEM_E_ARG, "smem_pair: a secondary past its list, or a negative score");
+    }
+    std::vector<double> tab((size_t)std::max<uint64_t>(n_tab, 1));
+    for (int d = 0; d < 4; ++d) {
+        if (pes[d].failed || pes[d].high < pes[d].low) continue;
+        double* t = tab.data() + dirs[d].tab_off;
+        for (int64_t dist = pes[d].low; dist <= pes[d].high; ++dist) {
+            t[dist - pes[d].low] = pair_pen(pes[d], dist, opt->a);
+        }
+    }
+    DevBuf<smem::AlnReg> dregs;
+    DevBuf<uint64_t> dregoff;
+    DevBuf<int64_t> dids;
+    DevBuf<double> dtab;
+    DevBuf<smem::PairDir> ddirs;
+    DevBuf<uint32_t> dctr, dlane, dwave;
+    DevBuf<smem::PairSel> dsel;
+    std::vector<uint64_t> off0;
+    Events<2> ev;
+    DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
+    if (call.rc) return call.rc;
+    const hipStream_t st = call.st;
+    if (int rc = fin_tables(g)) return rc;
+    HIP_TRY(ev.create());
+    HIP_TRY(dregs.ensure(n_regs));
+    HIP_TRY(dregoff.ensure(n_reads + 1));
+    if (ids) HIP_TRY(dids.ensure((size_t)n_pairs));
+    HIP_TRY(dtab.ensure(tab.size()));
+    HIP_TRY(ddirs.ensure(4));
+    HIP_TRY(dctr.ensure(4));
+    HIP_TRY(dlane.ensure((size_t)n_pairs));
+    HIP_TRY(dwave.ensure((size_t)n_pairs));
+    HIP_TRY(dsel.ensure((size_t)n_pairs));
+    const uint64_t* h_off = reg_off;
+    if (r0) {  // the kernels index regs from 0
+        off0.resize(n_reads + 1);
+        for (size_t r = 0; r <= n_reads; ++r) off0[r] = reg_off[r] - r0;
+        h_off = off0.data();
+    }
+    if (n_regs) HIP_TRY(hipMemcpyAsync(dregs.p, regs + r0, sizeof(smem::AlnReg) * n_regs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dregoff.p, h_off, 8 * (n_reads + 1), hipMemcpyHostToDevice, st));
+    if (ids) HIP_TRY(hipMemcpyAsync(dids.p, ids, sizeof(int64_t) * (size_t)n_pairs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dtab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ddirs.p, dirs, sizeof(dirs), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dctr.p, 0, sizeof(uint32_t) * 4, st));
+    smem::PairParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.regs = dregs.p, P.reg_off = dregoff.p, P.ids = ids ? dids.p : nullptr, P.id0 = id0, P.l_pac = l_pac;
+    P.n_pairs = n_pairs;
+    P.a = opt->a, P.b = opt->b, P.o_del = opt->o_del, P.e_del = opt->e_del, P.o_ins = opt->o_ins, P.e_ins = opt->e_ins;
+    P.pen_unpaired = opt->pen_unpaired, P.T = opt->T, P.min_seed_len = opt->min_seed_len;
+    P.mapQ_coef_fac = opt->mapQ_coef_fac, P.mapQ_coef_len = opt->mapQ_coef_len;
+    P.nopairing = !!(opt->flags & SMEM_PAIR_F_NOPAIRING);
+    P.log_tab = g->d_fin_log, P.subn_tab = g->d_fin_subn, P.dirs = ddirs.p, P.pen = dtab.p;
+    P.ctr = dctr.p, P.lane_list = dlane.p, P.wave_list = dwave.p, P.sel = dsel.p;
+    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(smem_launch_pair_split(&P, st));
+    HIP_TRY(smem_launch_pair_lane(&P, st));
+    HIP_TRY(smem_launch_pair_wave(&P, g->n_cu, st));
+    HIP_TRY(hipEventRecord(ev[1], st));
+    HIP_TRY(hipMemcpyAsync(sel, dsel.p, sizeof(smem::PairSel) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+    INJECT(ST_PAIR);
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    if (kernel_ms) *kernel_ms = ms;
     return SMEM_OK;
 }
 

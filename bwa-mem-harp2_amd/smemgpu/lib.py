@@ -46,6 +46,7 @@ EXPORTED = [
     "smem_gpu_load_contig_names", "smem_batch_set_read_text", "smem_batch_sam", "smem_batch_sam_results",
     "smem_sam_text", "smem_batch_sam_stats",
     "smem_ksw_align2_long", "smem_matesw_opt_default", "smem_matesw", "smem_gpu_cu_count",
+    "smem_pestat_opt_default", "smem_pestat", "smem_pair_opt_default", "smem_pair",
     "smem_occ_narrow_ok", "smem_occ64_host", "smem_extend_host",
 ]
 
@@ -223,6 +224,54 @@ def matesw_opt(**kw) -> MateswOptT:
     return o
 
 
+class PestatOptT(C.Structure):
+    """smem_pestat_opt_t: the mem_opt_t fields mem_pestat reads"""
+    _fields_ = [("a", C.c_int32), ("min_seed_len", C.c_int32), ("max_ins", C.c_int32), ("mask_level", C.c_float),
+                ("pad", C.c_int32 * 2)]
+
+
+class PairOptT(C.Structure):
+    """smem_pair_opt_t: the mem_opt_t fields mem_pair and the decision block of mem_sam_pe read"""
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("o_del", C.c_int32), ("e_del", C.c_int32), ("o_ins", C.c_int32),
+                ("e_ins", C.c_int32), ("pen_unpaired", C.c_int32), ("T", C.c_int32), ("min_seed_len", C.c_int32),
+                ("mapQ_coef_len", C.c_float), ("mapQ_coef_fac", C.c_int32), ("flags", C.c_int32)]
+
+
+PESTAT_MAX_INS = 65535   # SMEM_PESTAT_MAX_INS
+PESTAT_WAVES_PER_CU = 8  # the statistics kernel's grid: this many waves of 64 pairs a CU (csrc/pair_kernels.h)
+PAIR_TAB_LEN = 65536     # SMEM_PAIR_TAB_LEN
+PAIR_LANE_MAX = 16       # pairs of up to this many regions in both lists are done a pair per lane
+PAIR_WAVES_PER_CU = 4    # the long pairs' grid (csrc/pair_kernels.h)
+PAIR_F_NOPAIRING = 1     # SMEM_PAIR_F_NOPAIRING
+PAIR_HOST = 1            # SMEM_PAIR_HOST: the pair is the caller's
+# smem_pestat_t and smem_pair_sel_t
+PESTAT_DT = np.dtype([("low", "<i4"), ("high", "<i4"), ("failed", "<i4"), ("pad", "<i4"), ("avg", "<f8"), ("std", "<f8")])
+PAIR_SEL_DT = np.dtype([("status", "<i4"), ("branch", "<i4"), ("z", "<i4", (2,)), ("mapq", "<i4", (2,)),
+                        ("proper", "<i4"), ("o", "<i4"), ("subo", "<i4"), ("n_sub", "<i4"), ("sub", "<i4", (2,)),
+                        ("promoted", "<i4", (2,))])
+
+
+def pestat_opt(**kw) -> PestatOptT:
+    """smem_pestat_opt_default (mem_opt_init, software/bwamem.c:48-75) with the named fields overridden"""
+    o = PestatOptT()
+    load().smem_pestat_opt_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def pair_opt(**kw) -> PairOptT:
+    """smem_pair_opt_default with the named fields overridden; nopairing sets the flag bit"""
+    o = PairOptT()
+    load().smem_pair_opt_default(C.byref(o))
+    for k, v in kw.items():
+        if k == "nopairing":
+            o.flags = (o.flags | PAIR_F_NOPAIRING) if v else (o.flags & ~PAIR_F_NOPAIRING)
+        else:
+            setattr(o, k, v)
+    return o
+
+
 SEED_DT = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4")])          # smem_seed_t = mem_seed_t
 CHAIN_DT = np.dtype([("pos", "<i8"), ("seed_off", "<u8"), ("n", "<i4"), ("pad", "<i4")])  # smem_chain_t
 # smem_alnreg_t = mem_alnreg_t (the 64-byte records chain2aln returns)
@@ -347,6 +396,14 @@ def load() -> C.CDLL:
     lib.smem_matesw.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int64, P(MateswOptT), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, P(C.c_uint64), P(C.c_double)]
+    lib.smem_pestat_opt_default.argtypes = [P(PestatOptT)]
+    lib.smem_pestat_opt_default.restype = None
+    lib.smem_pestat.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, P(PestatOptT), C.c_void_p,
+                                C.c_void_p, P(C.c_double)]
+    lib.smem_pair_opt_default.argtypes = [P(PairOptT)]
+    lib.smem_pair_opt_default.restype = None
+    lib.smem_pair.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                              P(PairOptT), C.c_void_p, P(C.c_double)]
     lib.smem_gpu_load_pac.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.smem_batch_chain2aln.argtypes = [C.c_void_p, C.c_void_p]
     lib.smem_batch_aln_results.argtypes = [C.c_void_p, P(C.c_void_p), P(P(C.c_uint64)), P(C.c_uint64)]
@@ -942,6 +999,62 @@ class Gpu:
                 raise err
             _check(rc, "smem_matesw")
             return out[:int(need.value)], reg_off_out, n_sw[:n_pairs], status[:n_pairs], ms.value
+
+    @staticmethod
+    def _pair_lists(what, regs, reg_off):
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.uint64)
+        regs = np.ascontiguousarray(regs)
+        if regs.dtype != ALNREG_DT:
+            regs = np.frombuffer(regs.astype(np.uint8, copy=False).tobytes(), dtype=ALNREG_DT)
+        if reg_off.size < 1 or reg_off.size % 2 != 1:
+            raise SmemError(f"{what}: reg_off needs 2 n_pairs + 1 entries")
+        if int(reg_off.max()) > regs.size:
+            raise SmemError(f"{what}: reg_off ends past regs")
+        return regs, reg_off, (reg_off.size - 1) // 2
+
+    def pestat(self, regs, reg_off, l_pac: int, opt: "PestatOptT" = None) -> tuple:
+        """mem_pestat (software/bwamem_pair.c:46-107) on this device (smem_pestat): reads 2p and
+        2p + 1 are pair p, regs (ALNREG_DT) / reg_off each read's list after mem_sort_and_dedup.
+        Returns (pes as four PESTAT_DT records, n_cand[4], kernel ms)."""
+        regs, reg_off, n_pairs = self._pair_lists("pestat", regs, reg_off)
+        if opt is None:
+            opt = pestat_opt()
+        pes = np.zeros(4, dtype=PESTAT_DT)
+        n_cand = np.zeros(4, dtype=np.uint64)
+        ms = C.c_double()
+        _check(load().smem_pestat(self._h, n_pairs, regs.ctypes.data, reg_off.ctypes.data, int(l_pac), C.byref(opt),
+                                  pes.ctypes.data, n_cand.ctypes.data, C.byref(ms)), "smem_pestat")
+        return pes, n_cand, ms.value
+
+    def pair(self, regs, reg_off, l_pac: int, pes, opt: "PairOptT" = None, ids=None, id0: int = 0) -> tuple:
+        """mem_pair and the decision block of mem_sam_pe (software/bwamem_pair.c:177-236, 266-304,
+        321-326) of every pair on this device (smem_pair): regs / reg_off each read's list after
+        mem_mark_primary_se (Gpu.reg_finalize's order), pes what Gpu.pestat returned (PESTAT_DT),
+        four PestatT or four (low, high, failed, avg, std) tuples, ids the pairs' ids (None: id0 + p).
+        Returns (PAIR_SEL_DT per pair, kernel ms)."""
+        regs, reg_off, n_pairs = self._pair_lists("pair", regs, reg_off)
+        if isinstance(pes, np.ndarray) and pes.dtype == PESTAT_DT:
+            pe = np.ascontiguousarray(pes)
+        else:
+            pe = np.zeros(4, dtype=PESTAT_DT)
+            for r in range(4):
+                x = pes[r]
+                t = (x.low, x.high, x.failed, x.avg, x.std) if hasattr(x, "low") else tuple(x)
+                pe[r]["low"], pe[r]["high"], pe[r]["failed"], pe[r]["avg"], pe[r]["std"] = t
+        if pe.size != 4:
+            raise SmemError("pair: pes needs four orientations")
+        if opt is None:
+            opt = pair_opt()
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            if ids.size != n_pairs:
+                raise SmemError("pair: one id per pair")
+        sel = np.zeros(max(n_pairs, 1), dtype=PAIR_SEL_DT)
+        ms = C.c_double()
+        _check(load().smem_pair(self._h, n_pairs, regs.ctypes.data, reg_off.ctypes.data,
+                                ids.ctypes.data if ids is not None else None, int(id0), int(l_pac), pe.ctypes.data,
+                                C.byref(opt), sel.ctypes.data, C.byref(ms)), "smem_pair")
+        return sel[:n_pairs], ms.value
 
     def load_pac(self, pac, l_pac: int) -> None:
         """Keep the 2-bit .pac resident in HBM (smem_gpu_load_pac)."""

@@ -28,7 +28,7 @@
  * caller that takes its CPU path on SMEM_E_DEVICE computes exactly what the
  * reference computes.  Allocation failures are SMEM_E_NOMEM and leave the
  * device usable.  SMEM_GPU_FAIL=<stage>:<k>[:sticky] (stage: upload, seed,
- * sa, chain, aln, fin, g2a, sam, matesw, fetch, any) injects SMEM_E_DEVICE into every k-th
+ * sa, chain, aln, fin, g2a, sam, matesw, pair, fetch, any) injects SMEM_E_DEVICE into every k-th
  * call of the stage after its work is enqueued, to test that contract.
  */
 #ifndef SMEM_GPU_H
@@ -647,8 +647,8 @@ int  smem_batch_fin_results(const smem_batch_t *b, const smem_alnreg_t **regs_ou
  * that has not failed and that no region of the mate's current list already fills, the hit
  * inserted before the first lower score, then mem_sort_and_dedup.  End 0's anchors change end 1's
  * list; end 1's anchors then change end 0's.
- * mem_pestat_t (software/bwamem.h:78-82); the stage reads low, high and failed, which the caller
- * computes (mem_pestat stays on the host). */
+ * mem_pestat_t (software/bwamem.h:78-82); the stage reads low, high and failed, which
+ * smem_pestat computes. */
 typedef struct {
 	int32_t low, high, failed, pad;
 	double avg, std;
@@ -678,6 +678,90 @@ int  smem_matesw(smem_gpu_t *gpu, int n_pairs, const uint8_t *codes, const uint6
                  const uint64_t *reg_off, const smem_pestat_t pes[4], const uint8_t *pac, int64_t l_pac,
                  const smem_matesw_opt_t *opt, smem_alnreg_t *regs_out, uint64_t regs_cap, uint64_t *reg_off_out,
                  int32_t *n_sw, int32_t *status, uint64_t *n_regs_out, double *kernel_ms);
+
+/* ------------------------------------------- insert-size statistics and pairing */
+/* the mem_opt_t fields mem_pestat reads */
+typedef struct {
+	int32_t a, min_seed_len;  /* 1, 19 */
+	int32_t max_ins;          /* 10000; 1 .. SMEM_PESTAT_MAX_INS */
+	float mask_level;         /* 0.50 */
+	int32_t pad[2];
+} smem_pestat_opt_t;
+void smem_pestat_opt_default(smem_pestat_opt_t *opt);
+#define SMEM_PESTAT_MAX_INS 65535
+/* mem_pestat (software/bwamem_pair.c:46-107).  Host buffers in and out.  Reads 2p and 2p + 1 are
+ * pair p; regs / reg_off[2 n_pairs + 1] are each read's list as mem_align1_core leaves it (after
+ * mem_sort_and_dedup, before mem_mark_primary_se), smem_matesw's input.  On the device, a lane per
+ * pair (:52-63): a pair with an empty end is skipped, cal_sub (:32-44) of both ends -- a sequential
+ * scan over a list of any length that stops at the first significant overlap, the float product
+ * min_l * mask_level compared as the reference compares it --, the two tests against MIN_RATIO *
+ * score in double, mem_infer_dir of the two first regions, and where 0 < is <= max_ins one count
+ * into a histogram hist[dir][is].  The histogram, 4 * (max_ins + 1) counts, is what crosses to the
+ * host, which runs :64-106 over it in ascending order and in the reference's order of operations:
+ * the sum of squares takes one addition per pair, value by value, as the loop over the sorted
+ * array does.  pes[d]: low, high, failed, avg and std as mem_pestat leaves them (d = FF, FR, RF,
+ * RR), a failed orientation all zeros apart from failed; n_cand[d]: the "# candidate unique
+ * pairs".  n_pairs == 0 is valid and gives four failed orientations.  SMEM_E_ARG: max_ins < 1 or
+ * > SMEM_PESTAT_MAX_INS, a < 1, min_seed_len < 0, a mask_level that is NaN, reg_off that does not
+ * ascend, a missing buffer. */
+int  smem_pestat(smem_gpu_t *gpu, int n_pairs, const smem_alnreg_t *regs, const uint64_t *reg_off,
+                 int64_t l_pac, const smem_pestat_opt_t *opt, smem_pestat_t pes[4],
+                 uint64_t n_cand[4], double *kernel_ms);
+
+/* the mem_opt_t fields mem_pair, the decision block of mem_sam_pe and mem_approx_mapq_se read */
+typedef struct {
+	int32_t a, b;                      /* 1, 4 */
+	int32_t o_del, e_del, o_ins, e_ins;/* 6, 1, 6, 1 */
+	int32_t pen_unpaired;              /* 17 */
+	int32_t T;                         /* 30 */
+	int32_t min_seed_len;              /* 19 */
+	float mapQ_coef_len;               /* 50 */
+	int32_t mapQ_coef_fac;             /* 3 */
+	int32_t flags;                     /* SMEM_PAIR_F_* */
+} smem_pair_opt_t;
+#define SMEM_PAIR_F_NOPAIRING 1        /* MEM_F_NOPAIRING */
+void smem_pair_opt_default(smem_pair_opt_t *opt);
+#define SMEM_PAIR_TAB_LEN 65536        /* the longest range high - low + 1 of a live orientation */
+#define SMEM_PAIR_HOST    1
+/* what mem_sam_pe decides about one pair between mate rescue and mem_reg2aln (:266-304, :321-326) */
+typedef struct {
+	int32_t status;      /* 0, or SMEM_PAIR_HOST: the pair is the caller's and every other field is 0 -- an
+	                        end of more than SMEM_FIN_MAX_REGS regions; n_sub >= SMEM_FIN_TAB_LEN where line
+	                        282 needs its logarithm; an argument of mem_approx_mapq_se outside the finalize
+	                        stage's tables (smem_fin_sel_t's cases) for a region lines 292, 302-303 score */
+	int32_t branch;      /* 0: no pairing (MEM_F_NOPAIRING, an empty end, mem_pair returned 0, or is_multi of
+	                        either end, :271-276); 1: the paired alignment is preferred (o > score_un, :286);
+	                        2: the unpaired one (:300) */
+	int32_t z[2];        /* the regions to print, as indices into each end's list: mem_pair's in branch 1,
+	                        0, 0 otherwise */
+	int32_t mapq[2];     /* q_se after :294-299 (branch 1) or :302-303 (branch 2); -1 in branch 0, where the
+	                        single-end selection has them */
+	int32_t proper;      /* extra_flag & 2.  Branch 0: the test of :324-325 on the two first regions, made
+	                        where both ends have one with score >= T and 0 elsewhere; h[0].rid == h[1].rid
+	                        >= 0 of :321 needs the alignments' contigs and stays the caller's AND */
+	int32_t o, subo, n_sub;   /* as mem_pair returns them (subo before :280's max); 0 where it did not run */
+	int32_t sub[2], promoted[2];   /* branch 1: the chosen region's sub after :291 and whether its secondary
+	                        became -2; the lists are not written back */
+} smem_pair_sel_t;
+/* mem_pair (:177-236) and the decision block around it for every pair, on the GPU.  Host buffers
+ * in and out.  regs / reg_off[2 n_pairs + 1] are each read's list after mem_mark_primary_se(...,
+ * id << 1 | end), the order smem_reg_finalize writes, with secondary (an index into the read's
+ * list, or < 0), sub, sub_n and csub set; ids[p] the pair's id (NULL: id0 + p), (n_processed >> 1)
+ * + i of software/bwamem.c:1609 -- an int in mem_pair, so its low 32 bits count; pes: smem_pestat's
+ * result.  Before the launch the host fills, for every orientation that has not failed, pen[d][dist
+ * - low] = .721 * log(2. * erfc(fabs((dist - avg) / std) * M_SQRT1_2)) * a for dist in [low, high]
+ * with its own libm; the device adds (double)(s_i + s_k), the entry and .499, two IEEE additions,
+ * and truncates -- a sum that is not finite or is negative gives q = 0.  Keys (:186-187) are sorted
+ * as 128-bit pairs; the walk-back scan (:194-220) is the reference's; the array u is not built: the
+ * largest (q << 32 | hash, k << 32 | i), the second's q and n_sub are kept.  A pair of up to 16
+ * regions in both lists is done by one lane, a longer one by one wave with the keys in LDS.
+ * sel: one per pair.  SMEM_E_ARG (before any device work): a range high - low + 1 above
+ * SMEM_PAIR_TAB_LEN in an orientation that has not failed, reg_off that does not ascend, a
+ * secondary at or past its list's length, a negative score, a < 1, b < 0, unknown flags, a
+ * mapQ_coef_len that is NaN, a missing buffer. */
+int  smem_pair(smem_gpu_t *gpu, int n_pairs, const smem_alnreg_t *regs, const uint64_t *reg_off,
+               const int64_t *ids, int64_t id0, int64_t l_pac, const smem_pestat_t pes[4],
+               const smem_pair_opt_t *opt, smem_pair_sel_t *sel, double *kernel_ms);
 
 /* ------------------------------------------- alignments -> SAM text */
 /* The text mem_reg2sam_se(opt, bns, pac, s, a, 0, 0) leaves in s->sam (software/bwamem.c:1359-1393,
