@@ -1,6 +1,7 @@
 // Alignments -> single-end SAM text on the device: mem_reg2sam_se (software/bwamem.c:1359-1393)
 // through mem_aln2sam (:1214-1327) with extra_flag 0 and no mate, over the records
-// smem_batch_reg_finalize and smem_batch_reg2aln left in HBM (or a caller's host buffers).
+// smem_batch_reg_finalize and smem_batch_reg2aln left in HBM (or a caller's host buffers); and
+// the paired-end text of mem_sam_pe's tail over a caller's host buffers (SamPeParams below).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -70,10 +71,27 @@ struct SamParams {
     uint32_t* cnt;              // [SAM_CNTS]
 };
 
+// ---- the paired-end text (mem_sam_pe's tail, software/bwamem_pair.c:305-331; mem_aln2sam with a
+// mate, software/bwamem.c:1219-1260).  Reads 2p and 2p + 1 are pair p.
+// what the stage takes from smem_pair_sel_t: mode is the branch (0..2), or -1 for a pair that
+// is the host's; mapq[e] is printed in branch 1 and 2; proper is extra_flag & 2 before the AND of :321
+struct SamPair {
+    int32_t mode, mapq[2], proper;
+};
+
+struct SamPeParams {
+    SamParams s;                // n_reads == 2 n_pairs, recs set
+    const SamPair* pairs;       // [n_pairs]
+    uint32_t* rlen;             // [n_rec]: get_rlen of every record's CIGAR (the length pass writes it)
+};
+
 }  // namespace smem
 
 // the length pass: sam_len_kernel (one lane per record), then sam_read_kernel (one lane per read)
 extern "C" hipError_t smem_launch_sam_len(const smem::SamParams* P, hipStream_t st);
 // the write pass over text_off (the scan of read_bytes)
 extern "C" hipError_t smem_launch_sam_write(const smem::SamParams* P, hipStream_t st);
+// the same two passes of the paired-end text: sam_len_pe_kernel, sam_read_pe_kernel; sam_write_pe_kernel
+extern "C" hipError_t smem_launch_sam_pe_len(const smem::SamPeParams* X, hipStream_t st);
+extern "C" hipError_t smem_launch_sam_pe_write(const smem::SamPeParams* X, hipStream_t st);
 extern "C" hipError_t smem_preload_sam(void);

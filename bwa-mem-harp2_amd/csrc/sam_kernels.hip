@@ -1,9 +1,12 @@
-// Alignments -> single-end SAM text (csrc/sam_kernels.h): a length pass (one lane per record,
+// Alignments -> SAM text (csrc/sam_kernels.h), single-end and paired-end: a length pass (one lane per record,
 // then one lane per read), the offset scan of smem_kernels.hip over the reads' byte counts, and
 // a write pass, one wave per read: the wave assembles the read's lines in an LDS window that
 // follows the output stream 16 bytes at a time and stores every whole 16-byte chunk with one
 // dwordx4 store per lane; only the bytes before the first and after the last 16-byte boundary
 // of a read's text (they share their chunk with a neighbouring read's text) are stored singly.
+// The paired-end text has kernels of its own (sam_len_pe_kernel, sam_read_pe_kernel,
+// sam_write_pe_kernel) over the same helpers: every line also carries what mem_aln2sam takes
+// from the mate, record 0 of the pair's other read.
 #include "sam_kernels.h"
 
 namespace smem {
@@ -101,7 +104,21 @@ __device__ inline uint32_t tail_len(const SamParams& P, uint32_t r) {
 }
 
 // ---- the length pass
-__global__ __launch_bounds__(256) void sam_len_kernel(SamParams P) {
+// get_rlen (software/bwamem.c:1203-1212): the M and D lengths of a CIGAR, an int as the reference's
+__device__ inline int cigar_rlen(const uint32_t* w, int n) {
+    int l = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t op = w[i] & 0xf;
+        if (op == 0 || op == 2) l += (int)(w[i] >> 4);
+    }
+    return l;
+}
+
+// one lane per record.  PE (the paired-end text): the record's MAPQ is the pair's in branch 1 and
+// 2, its reference length is kept, and the bytes of FLAG, RNEXT, PNEXT and TLEN -- they depend on
+// the mate's record -- are left to sam_read_pe_kernel
+template <bool PE>
+__device__ __forceinline__ void sam_len_record(const SamParams& P, const SamPair* pairs, uint32_t* rlen) {
     const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= P.n_rec) return;
     // the read of record k: rec_off[r] <= k < rec_off[r + 1]
@@ -113,11 +130,16 @@ __global__ __launch_bounds__(256) void sam_len_kernel(SamParams P) {
     }
     const uint32_t r = lo;
     const Aln A = P.alns[k];
-    const RecV V = rec_of(P, k);
+    RecV V = rec_of(P, k);
+    if (PE) {
+        const SamPair S = pairs[r >> 1];
+        if (S.mode > 0) V.mapq = (r & 1u) ? S.mapq[1] : S.mapq[0];   // h[e].mapq = q_se[e] (software/bwamem_pair.c:306-307)
+    }
     const int rid = P.rid[k];
     if (A.status != 0 || V.mapq == -1 || rid < 0 || rid >= P.n_ctg || A.n_cigar < 0) {
         P.rec_len[k] = 1u << 31;   // the read is the host's
         P.sa_len[k] = 0;
+        if (PE) rlen[k] = 0;
         return;
     }
     const int which = (int)(k - P.rec_off[r]);
@@ -127,9 +149,10 @@ __global__ __launch_bounds__(256) void sam_len_kernel(SamParams P) {
     const int flag = V.flag | (A.is_rev ? 0x10 : 0);
     const int64_t pos1 = A.pos - P.ctg_off[rid] + 1;
     const uint32_t coord = ctg_name_len(P, rid) + 1 + num_len(pos1) + 1;
-    uint32_t len = name_len_of(P, r) + 1 + num_len((flag & 0xffff) | (flag & 0x10000 ? 0x100 : 0)) + 1;
+    uint32_t len = name_len_of(P, r) + 1 + (PE ? 0u : num_len((flag & 0xffff) | (flag & 0x10000 ? 0x100 : 0))) + 1;
     len += coord + num_len(V.mapq) + 1 + cl;
-    len += 1 + 5 + 1;                               // the mate fields
+    len += 1 + (PE ? 0u : 5u) + 1;                  // the mate fields
+    if (PE) rlen[k] = (uint32_t)cigar_rlen(cg, A.n_cigar);
     if (flag & 0x100) {
         len += 3;
     } else {
@@ -145,6 +168,9 @@ __global__ __launch_bounds__(256) void sam_len_kernel(SamParams P) {
     // rname,pos,strand,CIGAR,mapq,NM; -- 0 marks a record no SA:Z lists (software/bwamem.c:1312)
     P.sa_len[k] = (flag & 0x100) ? 0u : coord + 2 + cl + 1 + num_len(V.mapq) + 1 + num_len(A.NM) + 1;
 }
+
+__global__ __launch_bounds__(256) void sam_len_kernel(SamParams P) { sam_len_record<false>(P, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void sam_len_pe_kernel(SamPeParams X) { sam_len_record<true>(X.s, X.pairs, X.rlen); }
 
 // bytes of the unmapped line (software/bwamem.c:1381-1385: rid -1, flag 4, AS:i:0, XS:i:0)
 __device__ inline uint64_t unmapped_len(const SamParams& P, uint32_t r) {
@@ -168,6 +194,119 @@ __global__ __launch_bounds__(256) void sam_read_kernel(SamParams P) {
     if (n_prim >= 2) tot += n_prim * 6 + (n_prim - 1) * sum_sa;
     if (lo == hi) tot = unmapped_len(P, r);
     P.read_bytes[r] = host ? 0 : tot;
+    P.status[r] = host ? SAM_HOST : 0;
+    if (host) atomicAdd(P.cnt + SAM_N_HOST, 1u);
+}
+
+// ---- the paired-end lines: mem_aln2sam with a mate (software/bwamem.c:1219-1260)
+// the mate of every line of read r: record 0 of read r ^ 1 (h[!e], software/bwamem_pair.c:306-307,
+// 316-320), or none for a read without a record (mem_reg2aln(.., 0): rid -1)
+struct Mate {
+    bool has;
+    int rid, is_rev, n_cigar, rlen;
+    int64_t pos;
+};
+__device__ __forceinline__ Mate mate_of(const SamPeParams& X, uint32_t r) {
+    const SamParams& P = X.s;
+    const uint64_t lo = P.rec_off[r ^ 1u], hi = P.rec_off[(r ^ 1u) + 1];
+    Mate M{hi > lo, -1, 0, 0, 0, -1};
+    if (M.has) {
+        const Aln A = P.alns[lo];
+        M.rid = P.rid[lo], M.is_rev = A.is_rev, M.n_cigar = A.n_cigar, M.rlen = (int)X.rlen[lo], M.pos = A.pos;
+    }
+    return M;
+}
+// extra_flag & 2 of read r's lines: the pair's own in branch 1 and 2; in branch 0 the test of
+// :324-325 counts only where h[0].rid == h[1].rid >= 0 (software/bwamem_pair.c:321)
+__device__ __forceinline__ int proper_of(const SamPeParams& X, uint32_t r, const Mate& M) {
+    const SamPair S = X.pairs[r >> 1];
+    if (!S.proper) return 0;
+    if (S.mode != 0) return 2;
+    const uint64_t lo = X.s.rec_off[r];
+    return lo < X.s.rec_off[r + 1] && M.has && X.s.rid[lo] == M.rid ? 2 : 0;
+}
+
+// what a line owes to the pair: its FLAG, and RNEXT (rid of the name; eq: '='; rid < 0: "*\t0\t0"),
+// PNEXT, TLEN
+struct PeLine {
+    int flag, mrid;
+    bool eq;
+    int64_t pnext, tlen;
+};
+// a record's line (software/bwamem.c:1221-1229, 1249-1260); vflag is the record's own flag
+__device__ __forceinline__ PeLine pe_line(const SamParams& P, uint32_t r, const Mate& M, int proper, int vflag, int rid,
+                                          const Aln& A, int rlen) {
+    PeLine L;
+    L.flag = vflag | 0x1 | (0x40 << (r & 1u)) | proper | (A.is_rev ? 0x10 : 0);
+    L.tlen = 0;
+    if (M.has) {
+        L.flag |= M.is_rev ? 0x20 : 0;
+        L.mrid = M.rid, L.eq = rid == M.rid, L.pnext = M.pos - P.ctg_off[M.rid] + 1;
+        if (L.eq && A.n_cigar != 0 && M.n_cigar != 0) {                                       // :1254-1258
+            const int64_t p0 = A.pos + (A.is_rev ? rlen - 1 : 0), p1 = M.pos + (M.is_rev ? M.rlen - 1 : 0);
+            L.tlen = -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0));
+        }
+    } else {  // copy alignment to mate (:1226-1227)
+        L.flag |= 0x8 | (A.is_rev ? 0x20 : 0);
+        L.mrid = rid, L.eq = true, L.pnext = A.pos - P.ctg_off[rid] + 1;
+    }
+    return L;
+}
+// the line of a read without a record: with a mapped mate it takes the mate's coordinate and
+// strand (copy mate to alignment, :1224-1225)
+__device__ __forceinline__ PeLine pe_line_unmapped(const SamParams& P, uint32_t r, const Mate& M) {
+    PeLine L;
+    L.flag = 0x4 | 0x1 | (0x40 << (r & 1u));
+    L.tlen = 0, L.eq = true, L.mrid = -1, L.pnext = 0;
+    if (M.has) {
+        L.flag |= M.is_rev ? 0x30 : 0;
+        L.mrid = M.rid, L.pnext = M.pos - P.ctg_off[M.rid] + 1;
+    } else {
+        L.flag |= 0x8;
+    }
+    return L;
+}
+__device__ __forceinline__ uint32_t flag_len(int flag) { return num_len((flag & 0xffff) | (flag & 0x10000 ? 0x100 : 0)); }
+// bytes of RNEXT, PNEXT and TLEN with the two tabs between them
+__device__ __forceinline__ uint32_t mate_len(const SamParams& P, const PeLine& L) {
+    if (L.mrid < 0) return 5;
+    return (L.eq ? 1u : ctg_name_len(P, L.mrid)) + 1 + num_len(L.pnext) + 1 + num_len(L.tlen);
+}
+
+// one lane per read: the pair is the host's when either read is; a record's line adds its FLAG
+// and mate fields; a read without a record prints the unmapped line or the placed one
+__global__ __launch_bounds__(256) void sam_read_pe_kernel(SamPeParams X) {
+    const SamParams& P = X.s;
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= P.n_reads) return;
+    const uint64_t lo = P.rec_off[r], hi = P.rec_off[r + 1];
+    bool host = X.pairs[r >> 1].mode < 0;
+    for (uint32_t q = r & ~1u; q <= (r | 1u); ++q) {
+        host |= (P.fin_status && P.fin_status[q] == FIN_REJECT) || P.offs[q + 1] == P.offs[q];
+        for (uint64_t k = P.rec_off[q]; k < P.rec_off[q + 1]; ++k) host |= (P.rec_len[k] >> 31) != 0;
+    }
+    uint64_t tot = 0;
+    if (!host) {  // (only now is every record of the pair known to have a contig)
+        const Mate M = mate_of(X, r);
+        if (lo == hi) {
+            const PeLine L = pe_line_unmapped(P, r, M);
+            const uint64_t l_seq = P.offs[r + 1] - P.offs[r];
+            const uint32_t coord = M.has ? ctg_name_len(P, M.rid) + 1 + num_len(L.pnext) + 4 : 7u;   // RNAME POS 0 *
+            tot = name_len_of(P, r) + 1 + flag_len(L.flag) + 1 + coord + 1 + mate_len(P, L) + 1 + l_seq + 1 +
+                  (P.qual ? l_seq : 1) + 7 + 7 + tail_len(P, r);
+        } else {
+            const int proper = proper_of(X, r, M);
+            uint64_t sum_sa = 0, n_prim = 0;
+            for (uint64_t k = lo; k < hi; ++k) {
+                const uint32_t sl = P.sa_len[k];
+                const PeLine L = pe_line(P, r, M, proper, rec_of(P, k).flag, P.rid[k], P.alns[k], (int)X.rlen[k]);
+                tot += (P.rec_len[k] & 0x7fffffffu) + flag_len(L.flag) + mate_len(P, L);
+                if (sl) n_prim += 1, sum_sa += sl;
+            }
+            if (n_prim >= 2) tot += n_prim * 6 + (n_prim - 1) * sum_sa;
+        }
+    }
+    P.read_bytes[r] = tot;
     P.status[r] = host ? SAM_HOST : 0;
     if (host) atomicAdd(P.cnt + SAM_N_HOST, 1u);
 }
@@ -301,15 +440,41 @@ SAM_INLINE void write_seq(const SamParams& P, Out& o, uint32_t r, int qb, int qe
     else o.emit(n, [q, qe](uint64_t i) { return q[qe - 1 - i]; });
 }
 
-// mem_aln2sam of list[which] = record k of read r (software/bwamem.c:1214-1327, m == 0)
+// what the lines of one read share in the paired-end text: the mate, extra_flag & 2, and the
+// MAPQ that replaces the record's in branch 1 and 2 (-1: none)
+struct PeRead {
+    const SamPeParams* X;
+    Mate M;
+    int proper, mapq;
+};
+
+// RNEXT, PNEXT and TLEN of a line (software/bwamem.c:1249-1260)
+SAM_INLINE void write_mate(const SamParams& P, Out& o, const PeLine& L) {
+    if (L.mrid < 0) {
+        o.lit(LIT("*\t0\t0"));
+        return;
+    }
+    if (L.eq) o.put('=');
+    else o.bytes(P.ctg_names + P.ctg_name_off[L.mrid], ctg_name_len(P, L.mrid));
+    o.put('\t'), o.num(L.pnext), o.put('\t'), o.num(L.tlen);
+}
+
+// mem_aln2sam of list[which] = record k of read r (software/bwamem.c:1214-1327); PE: with the
+// mate C->M, else m == 0
+template <bool PE>
 SAM_INLINE void write_record(const SamParams& P, Out& o, uint32_t r, uint64_t lo, uint64_t hi, uint64_t k,
-                                    bool others) {
+                                    bool others, const PeRead* C) {
     const Aln A = P.alns[k];
-    const RecV V = rec_of(P, k);
+    RecV V = rec_of(P, k);
     const int rid = P.rid[k], which = (int)(k - lo);
     const int l_seq = (int)(P.offs[r + 1] - P.offs[r]);
     const uint32_t* cg = P.cigar + A.cigar_off;
-    const int flag = V.flag | (A.is_rev ? 0x10 : 0);                                      // :1228
+    PeLine L;
+    if (PE) {
+        L = pe_line(P, r, C->M, C->proper, V.flag, rid, A, (int)C->X->rlen[k]);           // :1221-1229
+        if (C->mapq >= 0) V.mapq = C->mapq;
+    }
+    const int flag = PE ? L.flag : V.flag | (A.is_rev ? 0x10 : 0);                        // :1228
     o.bytes(P.names + P.name_off[r], name_len_of(P, r)), o.put('\t');                     // :1232
     o.num((flag & 0xffff) | (flag & 0x10000 ? 0x100 : 0)), o.put('\t');                   // :1233
     o.bytes(P.ctg_names + P.ctg_name_off[rid], ctg_name_len(P, rid)), o.put('\t');        // :1235
@@ -317,7 +482,8 @@ SAM_INLINE void write_record(const SamParams& P, Out& o, uint32_t r, uint64_t lo
     o.num(V.mapq), o.put('\t');                                                           // :1237
     if (A.n_cigar) o.cigar(cg, A.n_cigar, which != 0);                                    // :1238-1243
     else o.put('*');
-    o.lit(LIT("\t*\t0\t0\t"));                                                            // :1246, 1260-1261
+    if (PE) o.put('\t'), write_mate(P, o, L), o.put('\t');                                // :1246-1261
+    else o.lit(LIT("\t*\t0\t0\t"));                                                       // :1246, 1260-1261
     if (flag & 0x100) {                                                                   // :1264-1265
         o.lit(LIT("*\t*"));
     } else {
@@ -368,7 +534,46 @@ __global__ __launch_bounds__(64) void sam_write_kernel(SamParams P) {
         } else {
             uint32_t n_prim = 0;
             for (uint64_t k = lo; k < hi; ++k) n_prim += P.sa_len[k] != 0;
-            for (uint64_t k = lo; k < hi; ++k) write_record(P, o, r, lo, hi, k, n_prim >= 2);
+            for (uint64_t k = lo; k < hi; ++k) write_record<false>(P, o, r, lo, hi, k, n_prim >= 2, nullptr);
+        }
+        const bool bad = o.over || o.base + o.fill != t1;
+        o.flush(true);
+        if (bad && threadIdx.x == 0) atomicAdd(P.cnt + SAM_N_BADLEN, 1u);
+    }
+}
+
+// the paired-end text, one wave per read: every line against the read's mate
+__global__ __launch_bounds__(64) void sam_write_pe_kernel(SamPeParams X) {
+    const SamParams& P = X.s;
+    for (uint32_t r = blockIdx.x; r < P.n_reads; r += gridDim.x) {
+        const uint64_t t0 = P.text_off[r], t1 = P.text_off[r + 1];
+        if (t1 <= t0) continue;  // the host's pair
+        Out o;
+        o.text = P.text, o.base = t0 & ~15ull, o.end = t1, o.fill = o.skip = (uint32_t)(t0 & 15), o.over = false;
+        const uint64_t lo = P.rec_off[r], hi = P.rec_off[r + 1];
+        PeRead C;
+        C.X = &X, C.M = mate_of(X, r);
+        if (lo == hi) {  // t = mem_reg2aln(.., 0) against the mate: software/bwamem.c:1381-1385, 1224-1225
+            const PeLine L = pe_line_unmapped(P, r, C.M);
+            o.bytes(P.names + P.name_off[r], name_len_of(P, r)), o.put('\t');
+            o.num(L.flag), o.put('\t');
+            if (C.M.has) {                                                                // :1235-1237, 1244
+                o.bytes(P.ctg_names + P.ctg_name_off[L.mrid], ctg_name_len(P, L.mrid)), o.put('\t');
+                o.num(L.pnext), o.lit(LIT("\t0\t*\t"));
+            } else {
+                o.lit(LIT("*\t0\t0\t*\t"));                                               // :1245
+            }
+            write_mate(P, o, L), o.put('\t');
+            write_seq(P, o, r, 0, (int)(P.offs[r + 1] - P.offs[r]), C.M.has && C.M.is_rev);
+            o.lit(LIT("\tAS:i:0")), o.lit(LIT("\tXS:i:0"));                               // :1301-1302
+            write_rg(P, o);
+            write_end(P, o, r);
+        } else {
+            const SamPair S = X.pairs[r >> 1];
+            C.proper = proper_of(X, r, C.M), C.mapq = S.mode <= 0 ? -1 : (r & 1u) ? S.mapq[1] : S.mapq[0];
+            uint32_t n_prim = 0;
+            for (uint64_t k = lo; k < hi; ++k) n_prim += P.sa_len[k] != 0;
+            for (uint64_t k = lo; k < hi; ++k) write_record<true>(P, o, r, lo, hi, k, n_prim >= 2, &C);
         }
         const bool bad = o.over || o.base + o.fill != t1;
         o.flush(true);
@@ -387,10 +592,27 @@ extern "C" hipError_t smem_launch_sam_len(const smem::SamParams* P, hipStream_t 
     return hipGetLastError();
 }
 
+extern "C" hipError_t smem_launch_sam_pe_len(const smem::SamPeParams* X, hipStream_t st) {
+    const smem::SamParams& P = X->s;
+    if (P.n_rec)
+        hipLaunchKernelGGL(smem::sam_len_pe_kernel, dim3((unsigned)((P.n_rec + 255) / 256)), dim3(256), 0, st, *X);
+    if (P.n_reads)
+        hipLaunchKernelGGL(smem::sam_read_pe_kernel, dim3((unsigned)((P.n_reads + 255) / 256)), dim3(256), 0, st, *X);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t smem_launch_sam_write(const smem::SamParams* P, hipStream_t st) {
     if (P->n_reads == 0) return hipSuccess;
     const unsigned grid = P->n_reads < (uint32_t)smem::SAM_WRITE_BLOCKS_MAX ? P->n_reads : (unsigned)smem::SAM_WRITE_BLOCKS_MAX;
     hipLaunchKernelGGL(smem::sam_write_kernel, dim3(grid), dim3(64), 0, st, *P);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t smem_launch_sam_pe_write(const smem::SamPeParams* X, hipStream_t st) {
+    const uint32_t n = X->s.n_reads;
+    if (n == 0) return hipSuccess;
+    const unsigned grid = n < (uint32_t)smem::SAM_WRITE_BLOCKS_MAX ? n : (unsigned)smem::SAM_WRITE_BLOCKS_MAX;
+    hipLaunchKernelGGL(smem::sam_write_pe_kernel, dim3(grid), dim3(64), 0, st, *X);
     return hipGetLastError();
 }
 
@@ -400,5 +622,8 @@ extern "C" hipError_t smem_preload_sam(void) {
     hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(smem::sam_len_kernel));
     if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(smem::sam_read_kernel));
     if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(smem::sam_write_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(smem::sam_len_pe_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(smem::sam_read_pe_kernel));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(smem::sam_write_pe_kernel));
     return e;
 }

@@ -4165,13 +4165,20 @@ struct SamPass {
     hipEvent_t* ev = nullptr;        // 4 events
     int inject = -1;
     float ms_len = 0.f, ms_write = 0.f;
+    const smem::SamPair* pairs = nullptr;  // set: the paired-end kernels, with rlen
+    uint32_t* rlen = nullptr;
 };
 
 static int run_sam_len(SamPass& R, hipStream_t st) {
     const int n = (int)R.P.n_reads;
     HIP_TRY(hipMemsetAsync(R.P.cnt, 0, sizeof(uint32_t) * smem::SAM_CNTS, st));
     HIP_TRY(hipEventRecord(R.ev[0], st));
-    HIP_TRY(smem_launch_sam_len(&R.P, st));
+    if (R.pairs) {
+        const smem::SamPeParams X{R.P, R.pairs, R.rlen};
+        HIP_TRY(smem_launch_sam_pe_len(&X, st));
+    } else {
+        HIP_TRY(smem_launch_sam_len(&R.P, st));
+    }
     size_t tmp = R.scan_tmp->n;
     HIP_TRY(smem_launch_offsets(R.read_bytes, R.text_off, n, R.scan_tmp->p, &tmp, st));
     HIP_TRY(hipEventRecord(R.ev[1], st));
@@ -4184,7 +4191,12 @@ static int run_sam_len(SamPass& R, hipStream_t st) {
 
 static int run_sam_write(SamPass& R, hipStream_t st) {
     HIP_TRY(hipEventRecord(R.ev[2], st));
-    HIP_TRY(smem_launch_sam_write(&R.P, st));
+    if (R.pairs) {
+        const smem::SamPeParams X{R.P, R.pairs, R.rlen};
+        HIP_TRY(smem_launch_sam_pe_write(&X, st));
+    } else {
+        HIP_TRY(smem_launch_sam_write(&R.P, st));
+    }
     HIP_TRY(hipEventRecord(R.ev[3], st));
     HIP_TRY(hipMemcpyAsync(R.h_ctr + 1, R.P.cnt, sizeof(uint32_t) * smem::SAM_CNTS, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -4277,49 +4289,74 @@ int smem_batch_sam_stats(const smem_batch_t* b, smem_sam_stats_t* st) {
     return SMEM_OK;
 }
 
-int smem_sam_text(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_t* offs, const char* names,
-                  const uint64_t* name_off, const char* qual, const char* comments, const uint64_t* comment_off,
-                  const uint64_t* aln_off, const smem_aln_t* alns, const int32_t* rid, const smem_sam_rec_t* recs,
-                  const int32_t* fin_status, const uint32_t* cigar, uint64_t n_cigar_words, const char* md,
-                  uint64_t n_md_bytes, int n_seqs, const int64_t* ctg_offset, const char* ctg_names,
-                  const uint64_t* ctg_name_off, const smem_sam_opt_t* opt, char* text, uint64_t text_cap,
-                  uint64_t* text_off, int32_t* status, uint64_t* n_bytes, double* kernel_ms) {
+// smem_sam_text (pe false) and smem_sam_text_pe over the same host buffers: the checks, the
+// uploads and the two passes are shared; the paired-end call adds the pairs' checks, what the
+// kernels take from sel (smem::SamPair) and the records' reference lengths
+static int sam_text_host(const char* fn, smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_t* offs,
+                         const char* names, const uint64_t* name_off, const char* qual, const char* comments,
+                         const uint64_t* comment_off, const uint64_t* aln_off, const smem_aln_t* alns, const int32_t* rid,
+                         const smem_sam_rec_t* recs, const int32_t* fin_status, const uint32_t* cigar,
+                         uint64_t n_cigar_words, const char* md, uint64_t n_md_bytes, int n_seqs,
+                         const int64_t* ctg_offset, const char* ctg_names, const uint64_t* ctg_name_off,
+                         const smem_sam_opt_t* opt, char* text, uint64_t text_cap, uint64_t* text_off, int32_t* status,
+                         uint64_t* n_bytes, double* kernel_ms, bool pe, int n_pairs, const smem_pair_sel_t* sel) {
+    auto bad = [fn](int code, const char* what) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+        return fail(code, msg);
+    };
     g_err[0] = 0;
     // every check below is the host's: nothing touches a device before they have passed
     if (!g || n_reads < 0 || !n_bytes || !text_off || (text_cap > 0 && !text) ||
         (n_reads > 0 && (!codes || !offs || !names || !name_off || !aln_off || !status)) || (comments && !comment_off))
-        return fail(SMEM_E_ARG, "smem_sam_text: bad arguments");
+        return bad(SMEM_E_ARG, "bad arguments");
+    if (pe && (n_pairs < 0 || (int64_t)n_reads != 2 * (int64_t)n_pairs || (n_pairs > 0 && !sel)))
+        return bad(SMEM_E_ARG, "n_reads is not 2 * n_pairs, or no sel");
     const char* rg = opt && opt->rg_id ? opt->rg_id : "";
     const size_t rg_len = strlen(rg);
-    if (rg_len > SAM_RG_MAX) return fail(SMEM_E_ARG, "smem_sam_text: rg_id of more than 1023 bytes");
+    if (rg_len > SAM_RG_MAX) return bad(SMEM_E_ARG, "rg_id of more than 1023 bytes");
     if (kernel_ms) *kernel_ms = 0.0;
     *n_bytes = 0, text_off[0] = 0;
     if (n_reads == 0) return SMEM_OK;
-    if (aln_off[0] != 0) return fail(SMEM_E_ARG, "smem_sam_text: aln_off must start at 0");
+    if (aln_off[0] != 0) return bad(SMEM_E_ARG, "aln_off must start at 0");
     for (int r = 0; r < n_reads; ++r) {
         if (offs[r + 1] < offs[r] || offs[r + 1] - offs[r] > (1u << 30) || aln_off[r + 1] < aln_off[r] ||
             name_off[r + 1] < name_off[r] || (comments && comment_off[r + 1] < comment_off[r]))
-            return fail(SMEM_E_ARG, "smem_sam_text: offsets not ascending");
+            return bad(SMEM_E_ARG, "offsets not ascending");
         if (name_off[r + 1] - name_off[r] > (uint64_t)smem::SAM_NAME_MAX)
-            return fail(SMEM_E_ARG, "smem_sam_text: a name of more than 255 bytes");
+            return bad(SMEM_E_ARG, "a name of more than 255 bytes");
     }
     const uint64_t n_bases = offs[n_reads], n_rec = aln_off[n_reads];
-    if (n_rec >= (1ull << 31)) return fail(SMEM_E_CAPACITY, "smem_sam_text: too many records");
+    if (n_rec >= (1ull << 31)) return bad(SMEM_E_CAPACITY, "too many records");
     if (n_rec > 0 && (!alns || !rid || !recs || n_seqs <= 0 || !ctg_offset || !ctg_names || !ctg_name_off))
-        return fail(SMEM_E_ARG, "smem_sam_text: no record / contig arrays");
+        return bad(SMEM_E_ARG, "no record / contig arrays");
     for (uint64_t k = offs[0]; k < n_bases; ++k)
-        if (codes[k] > 4) return fail(SMEM_E_ARG, "smem_sam_text: query code > 4");
+        if (codes[k] > 4) return bad(SMEM_E_ARG, "query code > 4");
     if (n_rec > 0)
         for (int i = 0; i < n_seqs; ++i)
-            if (ctg_name_off[i + 1] < ctg_name_off[i]) return fail(SMEM_E_ARG, "smem_sam_text: ctg_name_off not ascending");
+            if (ctg_name_off[i + 1] < ctg_name_off[i]) return bad(SMEM_E_ARG, "ctg_name_off not ascending");
     for (uint64_t k = 0; k < n_rec; ++k) {
         const smem_aln_t& A = alns[k];
         if (A.status != 0) continue;  // the read goes to the host: nothing of the record is read
-        if (rid[k] < 0 || rid[k] >= n_seqs) return fail(SMEM_E_ARG, "smem_sam_text: a record's rid outside the contigs");
+        if (rid[k] < 0 || rid[k] >= n_seqs) return bad(SMEM_E_ARG, "a record's rid outside the contigs");
         if (A.n_cigar < 0 || A.md_len < 0 || A.cigar_off > n_cigar_words || (uint64_t)A.n_cigar > n_cigar_words - A.cigar_off ||
             A.md_off > n_md_bytes || (uint64_t)A.md_len > n_md_bytes - A.md_off || (A.n_cigar > 0 && !cigar) ||
             (A.md_len > 0 && !md))
-            return fail(SMEM_E_ARG, "smem_sam_text: a record's CIGAR or MD outside the pools");
+            return bad(SMEM_E_ARG, "a record's CIGAR or MD outside the pools");
+    }
+    std::vector<smem::SamPair> h_pairs;
+    if (pe) {
+        h_pairs.resize((size_t)n_pairs);
+        for (int p = 0; p < n_pairs; ++p) {
+            const smem_pair_sel_t& S = sel[p];
+            const uint64_t a0 = name_off[2 * p], a1 = name_off[2 * p + 1], a2 = name_off[2 * p + 2];
+            if (a1 - a0 != a2 - a1 || std::memcmp(names + a0, names + a1, a1 - a0) != 0)
+                return bad(SMEM_E_ARG, "paired reads have different names");   // software/bwamem_pair.c:310, 329
+            if (S.branch < 0 || S.branch > 2) return bad(SMEM_E_ARG, "a branch outside 0..2");
+            if (S.branch != 0 && (aln_off[2 * p + 1] - aln_off[2 * p] != 1 || aln_off[2 * p + 2] - aln_off[2 * p + 1] != 1))
+                return bad(SMEM_E_ARG, "a read of a pair in branch 1 or 2 without exactly one record");
+            h_pairs[(size_t)p] = smem::SamPair{S.status != 0 ? -1 : S.branch, {S.mapq[0], S.mapq[1]}, S.proper != 0};
+        }
     }
     const uint64_t N = (uint64_t)n_reads + 1, nn = name_off[n_reads], nc = comments ? comment_off[n_reads] : 0;
     const uint64_t nnc = n_rec ? ctg_name_off[n_seqs] : 0;
@@ -4331,6 +4368,8 @@ int smem_sam_text(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64
     DevBuf<smem::SamRec> drec;
     DevBuf<uint32_t> dcig, dreclen, dsalen, dcnt;
     DevBuf<int64_t> dctg;
+    DevBuf<smem::SamPair> dpairs;
+    DevBuf<uint32_t> drlen;
     Events<4> ev;
     DeviceCall call(g);  // (declared after the buffers: drained before they are freed)
     if (call.rc) return call.rc;
@@ -4364,6 +4403,11 @@ int smem_sam_text(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64
     HIP_TRY(dtoff.ensure(N));
     HIP_TRY(dstatus.ensure((uint64_t)n_reads));
     HIP_TRY(dtext.ensure(text_cap));
+    if (pe) {
+        HIP_TRY(dpairs.ensure((uint64_t)n_pairs));
+        HIP_TRY(drlen.ensure(NR));
+        HIP_TRY(hipMemcpyAsync(dpairs.p, h_pairs.data(), sizeof(smem::SamPair) * (size_t)n_pairs, hipMemcpyHostToDevice, st));
+    }
     size_t tmp = 0;
     HIP_TRY(smem_launch_offsets(nullptr, nullptr, n_reads, nullptr, &tmp, nullptr));
     HIP_TRY(dscan.ensure(tmp + 256));
@@ -4404,18 +4448,44 @@ int smem_sam_text(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64
     P.rec_len = dreclen.p, P.sa_len = dsalen.p, P.read_bytes = dbytes.p, P.status = dstatus.p;
     P.text_off = dtoff.p, P.cnt = dcnt.p, P.text = dtext.p;
     R.read_bytes = dbytes.p, R.text_off = dtoff.p, R.scan_tmp = &dscan, R.h_ctr = h_ctr, R.ev = ev.e, R.inject = ST_SAM;
+    if (pe) R.pairs = dpairs.p, R.rlen = drlen.p;
     if (int rc = run_sam_len(R, st)) return rc;
     if (kernel_ms) *kernel_ms = (double)R.ms_len;
     *n_bytes = h_ctr[0];
     HIP_TRY(hipMemcpyAsync(text_off, dtoff.p, 8 * N, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(status, dstatus.p, sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_ctr[0] > text_cap) return fail(SMEM_E_CAPACITY, "smem_sam_text: text buffer too small");
+    if (h_ctr[0] > text_cap) return bad(SMEM_E_CAPACITY, "text buffer too small");
     if (int rc = run_sam_write(R, st)) return rc;
     if (kernel_ms) *kernel_ms += (double)R.ms_write;
     if (h_ctr[0]) HIP_TRY(hipMemcpyAsync(text, dtext.p, h_ctr[0], hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return SMEM_OK;
+}
+
+int smem_sam_text(smem_gpu_t* g, int n_reads, const uint8_t* codes, const uint64_t* offs, const char* names,
+                  const uint64_t* name_off, const char* qual, const char* comments, const uint64_t* comment_off,
+                  const uint64_t* aln_off, const smem_aln_t* alns, const int32_t* rid, const smem_sam_rec_t* recs,
+                  const int32_t* fin_status, const uint32_t* cigar, uint64_t n_cigar_words, const char* md,
+                  uint64_t n_md_bytes, int n_seqs, const int64_t* ctg_offset, const char* ctg_names,
+                  const uint64_t* ctg_name_off, const smem_sam_opt_t* opt, char* text, uint64_t text_cap,
+                  uint64_t* text_off, int32_t* status, uint64_t* n_bytes, double* kernel_ms) {
+    return sam_text_host("smem_sam_text", g, n_reads, codes, offs, names, name_off, qual, comments, comment_off, aln_off,
+                         alns, rid, recs, fin_status, cigar, n_cigar_words, md, n_md_bytes, n_seqs, ctg_offset, ctg_names,
+                         ctg_name_off, opt, text, text_cap, text_off, status, n_bytes, kernel_ms, false, 0, nullptr);
+}
+
+int smem_sam_text_pe(smem_gpu_t* g, int n_pairs, const smem_pair_sel_t* sel, int n_reads, const uint8_t* codes,
+                     const uint64_t* offs, const char* names, const uint64_t* name_off, const char* qual,
+                     const char* comments, const uint64_t* comment_off, const uint64_t* aln_off, const smem_aln_t* alns,
+                     const int32_t* rid, const smem_sam_rec_t* recs, const int32_t* fin_status, const uint32_t* cigar,
+                     uint64_t n_cigar_words, const char* md, uint64_t n_md_bytes, int n_seqs, const int64_t* ctg_offset,
+                     const char* ctg_names, const uint64_t* ctg_name_off, const smem_sam_opt_t* opt, char* text,
+                     uint64_t text_cap, uint64_t* text_off, int32_t* status, uint64_t* n_bytes, double* kernel_ms) {
+    return sam_text_host("smem_sam_text_pe", g, n_reads, codes, offs, names, name_off, qual, comments, comment_off,
+                         aln_off, alns, rid, recs, fin_status, cigar, n_cigar_words, md, n_md_bytes, n_seqs, ctg_offset,
+                         ctg_names, ctg_name_off, opt, text, text_cap, text_off, status, n_bytes, kernel_ms, true, n_pairs,
+                         sel);
 }
 
 int smem_batch_stats(const smem_batch_t* b, smem_batch_stats_t* st) {

@@ -44,7 +44,7 @@ EXPORTED = [
     "smem_fin_opt_default", "smem_reg_finalize", "smem_batch_reg_finalize", "smem_batch_fin_results",
     "smem_gpu_load_contigs", "smem_batch_reg2aln", "smem_batch_aln2_results",
     "smem_gpu_load_contig_names", "smem_batch_set_read_text", "smem_batch_sam", "smem_batch_sam_results",
-    "smem_sam_text", "smem_batch_sam_stats",
+    "smem_sam_text", "smem_batch_sam_stats", "smem_sam_text_pe",
     "smem_ksw_align2_long", "smem_matesw_opt_default", "smem_matesw", "smem_gpu_cu_count",
     "smem_pestat_opt_default", "smem_pestat", "smem_pair_opt_default", "smem_pair",
     "smem_occ_narrow_ok", "smem_occ64_host", "smem_extend_host",
@@ -370,6 +370,8 @@ def load() -> C.CDLL:
                                                                                  C.c_void_p, P(SamOptT), C.c_void_p,
                                                                                  C.c_uint64, C.c_void_p, C.c_void_p,
                                                                                  P(C.c_uint64), P(C.c_double)]
+    if hasattr(lib, "smem_sam_text_pe"):
+        lib.smem_sam_text_pe.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + lib.smem_sam_text.argtypes[1:]
     lib.smem_chain_opt_default.argtypes = [P(ChainOptT)]
     lib.smem_chain_opt_default.restype = None
     lib.smem_batch_chain.argtypes = [C.c_void_p, C.c_int64, P(ChainOptT)]
@@ -1088,7 +1090,14 @@ class Gpu:
         cigar / md the pools alns points into, the contigs' offsets and names.  The text buffer
         starts at text_cap bytes (default: a guess) and the call is repeated with the size the
         library reports when it is too small (grow=False: SmemError with .n_bytes instead)."""
+        return self._sam_text(None, codes, offs, names, quals, comments, aln_off, alns, rid, recs, cigar, md, ctg_offsets,
+                              ctg_names, fin_status, rg_id, text_cap, grow)
+
+    def _sam_text(self, _sel, codes, offs, names, quals, comments, aln_off, alns, rid, recs, cigar, md, ctg_offsets,
+                  ctg_names, fin_status, rg_id, text_cap, grow) -> "SamResults":
+        """sam_text (_sel None) and sam_text_pe: one marshalling of the host buffers for both calls"""
         lib = load()
+        fn = "smem_sam_text" if _sel is None else "smem_sam_text_pe"
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         n = offs.size - 1
@@ -1129,20 +1138,36 @@ class Gpu:
             return a.ctypes.data if a is not None else None
         while True:
             text = np.zeros(max(cap, 1), dtype=np.uint8)
-            rc = lib.smem_sam_text(self._h, n, ptr(codes), ptr(offs), ptr(nm), ptr(nm_off), ptr(quals), ptr(cm),
-                                   ptr(cm_off), ptr(aln_off), ptr(alns), ptr(rid), ptr(recs), ptr(fin_status),
-                                   ptr(cigar), cigar.size, ptr(md), md.size, ctg_offsets.size, ptr(ctg_offsets), ptr(cn),
-                                   ptr(cn_off), C.byref(opt), ptr(text), cap, ptr(text_off), ptr(status), C.byref(nb),
-                                   C.byref(ms))
+            args = (n, ptr(codes), ptr(offs), ptr(nm), ptr(nm_off), ptr(quals), ptr(cm), ptr(cm_off), ptr(aln_off),
+                    ptr(alns), ptr(rid), ptr(recs), ptr(fin_status), ptr(cigar), cigar.size, ptr(md), md.size,
+                    ctg_offsets.size, ptr(ctg_offsets), ptr(cn), ptr(cn_off), C.byref(opt), ptr(text), cap, ptr(text_off),
+                    ptr(status), C.byref(nb), C.byref(ms))
+            if _sel is None:
+                rc = lib.smem_sam_text(self._h, *args)
+            else:
+                rc = lib.smem_sam_text_pe(self._h, _sel.size, ptr(_sel), *args)
             if rc == SMEM_E_CAPACITY and nb.value > cap and grow:
                 cap = int(nb.value)
                 continue
             if rc == SMEM_E_CAPACITY:
-                err = SmemError(f"smem_sam_text failed: SMEM_E_CAPACITY: the text needs {nb.value} bytes")
+                err = SmemError(f"{fn} failed: SMEM_E_CAPACITY: the text needs {nb.value} bytes")
                 err.n_bytes = int(nb.value)
                 raise err
-            _check(rc, "smem_sam_text")
+            _check(rc, fn)
             return SamResults(text[:int(nb.value)], text_off, status[:n], ms.value)
+
+    def sam_text_pe(self, sel, codes, offs, names, quals, comments, aln_off, alns, rid, recs, cigar, md, ctg_offsets,
+                    ctg_names, fin_status=None, rg_id=None, text_cap: int | None = None,
+                    grow: bool = True) -> "SamResults":
+        """The paired-end text of every pair over host buffers (smem_sam_text_pe: the tail of
+        mem_sam_pe, mem_aln2sam with a mate): sam_text's arguments with sel, the PAIR_SEL_DT array
+        Gpu.pair returns, one per pair; reads 2p and 2p + 1 are pair p.  Each read's records are
+        the finalize selection's list in branch 0 and the one alignment of region z[e] (flag 0,
+        xs = max(sub, csub)) in branch 1 and 2, where sel's mapq is printed.  Returns SamResults
+        as sam_text; both reads of a pair left to the caller have status SAM_HOST."""
+        sel = np.ascontiguousarray(sel, dtype=PAIR_SEL_DT)
+        return self._sam_text(sel, codes, offs, names, quals, comments, aln_off, alns, rid, recs, cigar, md, ctg_offsets,
+                              ctg_names, fin_status, rg_id, text_cap, grow)
 
     def chain2aln(self, pac, l_pac: int, codes, offs, chains, chain_off, seeds, opt) -> tuple:
         """mem_chain2aln_short / mem_chain2aln of every chain of every read

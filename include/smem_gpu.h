@@ -832,6 +832,37 @@ int  smem_sam_text(smem_gpu_t *gpu, int n_reads, const uint8_t *codes, const uin
                    const uint64_t *ctg_name_off, const smem_sam_opt_t *opt, char *text, uint64_t text_cap,
                    uint64_t *text_off, int32_t *status, uint64_t *n_bytes, double *kernel_ms);
 
+/* The paired-end text: the tail of mem_sam_pe (software/bwamem_pair.c:305-331) through mem_aln2sam
+ * with a mate (software/bwamem.c:1219-1260), smem_sam_text's arguments and conventions with n_pairs
+ * and sel, smem_pair's output unchanged.  Reads 2p and 2p + 1 are pair p (n_reads == 2 n_pairs).
+ * Records, per read, in smem_sam_text's layout: in branch 0 the finalize selection's list (it may
+ * be empty: mem_reg2sam_se prints the unmapped record); in branch 1 and 2 exactly one record, the
+ * alignment of region z[e] with xs = max(sub, csub) (sub after line 291) and flag 0 -- its
+ * recs[].mapq is ignored and sel[p].mapq[e] printed.  From sel[p] the stage takes status, branch,
+ * mapq and proper; it derives the rest: the mate of every line of read r is record 0 of read r ^ 1,
+ * or unmapped when that read has no record; 0x1, 0x40 / 0x80, 0x8, 0x20; 0x2 from proper, in branch
+ * 0 only where both reads have a record 0 on one contig (:321); an unmapped read whose mate is
+ * mapped prints the mate's RNAME and POS, MAPQ 0 and CIGAR *, and with a reverse mate 0x10 and its
+ * SEQ / QUAL reverse-complemented / reversed; a mapped read whose mate is not prints =, its own
+ * POS and 0 with 0x20 from its own strand; RNEXT is = or the mate's contig, PNEXT the mate's POS,
+ * TLEN -(p0 - p1 + sign(p0 - p1)) over the 5' ends (a reverse alignment adds the M and D lengths
+ * of its CIGAR less one), 0 across contigs or where either side has no CIGAR, per line against
+ * the same mate.  Everything from SEQ on is smem_sam_text's.
+ * status: a pair is the caller's (SMEM_SAM_HOST for both reads, zero bytes for both) when
+ * sel[p].status != 0 or either read meets one of smem_sam_text's conditions (in branch 1 and 2 a
+ * sel[p].mapq[e] of -1 stands for the record's).  SMEM_E_ARG, before any device work:
+ * n_reads != 2 n_pairs, a pair whose reads' names differ (err_fatal in the reference), a branch
+ * outside 0..2, a read of a pair in branch 1 or 2 without exactly one record, and smem_sam_text's
+ * cases.  SMEM_E_CAPACITY and its retry as smem_sam_text.  n_pairs == 0 is valid. */
+int  smem_sam_text_pe(smem_gpu_t *gpu, int n_pairs, const smem_pair_sel_t *sel, int n_reads, const uint8_t *codes,
+                      const uint64_t *offs, const char *names, const uint64_t *name_off, const char *qual,
+                      const char *comments, const uint64_t *comment_off, const uint64_t *aln_off,
+                      const smem_aln_t *alns, const int32_t *rid, const smem_sam_rec_t *recs,
+                      const int32_t *fin_status, const uint32_t *cigar, uint64_t n_cigar_words, const char *md,
+                      uint64_t n_md_bytes, int n_seqs, const int64_t *ctg_offset, const char *ctg_names,
+                      const uint64_t *ctg_name_off, const smem_sam_opt_t *opt, char *text, uint64_t text_cap,
+                      uint64_t *text_off, int32_t *status, uint64_t *n_bytes, double *kernel_ms);
+
 /* ---------------------------------------------------------- telemetry */
 typedef struct {
 	double kernel_ms;        /* seeding kernel(s), HIP events on the batch stream */
